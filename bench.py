@@ -10,14 +10,24 @@ log-probability emissions already resident in HBM.  Multi-GPU: one process per G
 each aligning its own batch (per-file data parallel, weak scaling); the character
 vocabulary is broadcast over RCCL at start-up; no collective on the data path.
 
-Reported beside the value (rank 0):
-  roofline      dominant kernel's algorithmic HBM bytes / time vs 8 TB/s
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps,
+the --dump-outputs files, and the result line (rank 0) with
+  roofline      dominant kernel's algorithmic HBM bytes / time of the timed steps vs 8 TB/s
+                
+--full adds every other leg, each a run of its own beside the timed steps:
+  roofline      .avg_launch_us_events: an event pair around every launch (untimed pass)
   cpu_baseline  the reference algorithm with its per-timestep torch-CPU op structure
                 (oracle TorchPort, 1 thread) on a bounded sample of the same batch
   mae_ms        word/char-boundary MAE of the GPU result vs the CPU oracle (same emission)
-  extra         C-oracle throughput, saturated-batch roofline, end-to-end align()
+  extra         C-oracle throughput, saturated-batch roofline, end-to-end align(), the
+                config-3/4/5 legs and their CPU baselines (--no-cpu, --no-e2e, --no-scale and
+                --no-corpus drop groups of them)
+--dump-outputs DIR writes what the last timed step returned (wx_align_dp's five output arrays
+of rank 0's batch) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared
+array for array.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu] [--no-e2e] [--no-scale]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+                       [--full [--no-cpu] [--no-e2e] [--no-scale] [--no-corpus]]
 """
 import argparse
 import json
@@ -79,23 +89,19 @@ def pmc_traffic(kernel):
     return None, None
 
 
-def time_steps(plan, steps, warmup, dist_on):
+def time_steps(plan, steps, warmup, dist_on, per_launch=True):
     """W untimed warm-up steps, then exactly K steps between two barriers + synchronize; the
     device time comes from one event pair around the K steps (no per-step event commands
-    between the launches).  A separate, untimed pass with an event pair around every launch
-    gives the kernel's mean duration for the roofline (time_steps.last_launch_s)."""
+    between the launches).  With `per_launch`, a separate, untimed pass before them, with an
+    event pair around every launch, gives the kernel's mean duration for the roofline
+    (time_steps.last_launch_s; None without the pass)."""
     for _ in range(warmup):
         plan.run()
     torch.cuda.synchronize()
     stream = torch.cuda.current_stream()
-    # per-launch kernel time (roofline leg): events on the stream the kernel runs on
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(min(steps, 20))]
-    for a, b in ev:
-        a.record(stream)
-        plan.run()
-        b.record(stream)
-    torch.cuda.synchronize()
-    time_steps.last_launch_s = float(np.mean([a.elapsed_time(b) / 1000.0 for a, b in ev]))
+    time_steps.last_launch_s = None
+    if per_launch:
+        _per_launch_pass(plan, min(steps, 20), stream)
     if dist_on:
         torch.distributed.barrier()
     torch.cuda.synchronize()
@@ -111,6 +117,36 @@ def time_steps(plan, steps, warmup, dist_on):
     host_s = time.perf_counter() - t0
     dev_s = e0.elapsed_time(e1) / 1000.0
     return host_s, dev_s
+
+
+def _per_launch_pass(plan, n, stream):
+    """Per-launch kernel time (roofline leg): events on the stream the kernel runs on."""
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+    for a, b in ev:
+        a.record(stream)
+        plan.run()
+        b.record(stream)
+    torch.cuda.synchronize()
+    time_steps.last_launch_s = float(np.mean([a.elapsed_time(b) / 1000.0 for a, b in ev]))
+
+
+def dump_outputs(plan, where):
+    """--dump-outputs: the arrays the last plan.run() returned to its caller (wx_align_dp's
+    seg_start / seg_end / seg_score per token, t_start / status per segment), each as
+    <where>/<name>.npy in float64 (exact for the int32 ones).  The per-token entries of a
+    segment that did not align are not defined by the ABI: they are written as 0."""
+    os.makedirs(where, exist_ok=True)
+    b = plan.b
+    arrs = {"seg_start": plan.seg_start[: b.tok_off[-1]], "seg_end": plan.seg_end[: b.tok_off[-1]],
+            "seg_score": plan.seg_score[: b.tok_off[-1]], "t_start": plan.t_start[: b.S],
+            "status": plan.status[: b.S]}
+    arrs = {k: v.cpu().numpy().astype(np.float64) for k, v in arrs.items()}
+    for i in np.flatnonzero((arrs["status"].astype(np.int64) & 15) != 0):
+        for k in ("seg_start", "seg_end", "seg_score"):
+            arrs[k][b.tok_off[i]: b.tok_off[i + 1]] = 0.0
+        arrs["t_start"][i] = 0.0
+    for k, v in arrs.items():
+        np.save(os.path.join(where, k + ".npy"), v)
 
 
 def cpu_port_baseline(ems_cpu, toks, budget_s=15.0):
@@ -768,6 +804,11 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--segments", type=int, default=64)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output arrays as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (CPU baselines, MAE vs the oracle, saturated "
+                         "batches, end-to-end and corpus legs); --no-* drop groups of them")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-e2e", action="store_true")
     ap.add_argument("--no-scale", action="store_true")
@@ -776,6 +817,10 @@ def main():
     args = ap.parse_args()
     if args.host_share_leg:
         return host_share_leg(args.host_share_leg)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: the headline only
+        args.no_cpu = args.no_e2e = args.no_scale = args.no_corpus = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(_spawn_ranks(args))
@@ -826,7 +871,9 @@ def main():
     ems, toks = make_batch(rng, args.segments, T, V, 300, 500, device)
     batch = _lib.Batch(ems, toks, [0] * len(ems), device=device)
     plan = _lib.AlignPlan(batch)
-    host_s, dev_s = time_steps(plan, args.steps, args.warmup, dist_on)
+    host_s, dev_s = time_steps(plan, args.steps, args.warmup, dist_on, per_launch=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(plan, args.dump_outputs)
     step_s = max(host_s, dev_s) / args.steps
     step_s = _allreduce([step_s], "max")[0] if dist_on else step_s
     audio_per_step = float(sum(batch.Ts)) * FRAME_S * world  # seconds of audio aligned per step, all ranks
@@ -875,7 +922,7 @@ def main():
                                             f" (+{len(knames) - 1} more launches)"),
                          "bytes_per_launch": B, "avg_launch_us": launch_s * 1e6,
                          "avg_launch_us_source": "device time of the timed back-to-back launches / steps",
-                         "avg_launch_us_events": time_steps.last_launch_s * 1e6,
+                         "avg_launch_us_events": time_steps.last_launch_s * 1e6 if args.full else None,
                          "traffic_ratio": (traffic / B) if traffic else None},
         }
         out["roofline"]["dp"] = _lib.status_summary(plan.status[: batch.S])
@@ -888,9 +935,11 @@ def main():
         out["roofline"]["latency"] = {"bound": "dependent DP steps", "T": t_max, "cycles_per_step": STEP_CYCLES,
                                       "clock_GHz": ENGINE_PEAK_GHZ, "floor_us": floor_us,
                                       "achieved_us": launch_s * 1e6, "frac": floor_us / (launch_s * 1e6)}
-        mae, ntok, nbad = mae_vs_oracle([e.cpu().numpy() for e in ems], toks, plan)
-        out["mae_ms"] = mae
-        out["mae_detail"] = {"tokens": ntok, "segments_with_path_mismatch": nbad, "vs": "CPU oracle, same emission"}
+        if args.full:
+            mae, ntok, nbad = mae_vs_oracle([e.cpu().numpy() for e in ems], toks, plan)
+            out["mae_ms"] = mae
+            out["mae_detail"] = {"tokens": ntok, "segments_with_path_mismatch": nbad,
+                                 "vs": "CPU oracle, same emission"}
         extra = {}
         if ranks is not None:
             extra["ranks"] = {"world_size": world, "backend": "rccl" if backend == "nccl" else backend,

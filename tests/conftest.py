@@ -21,18 +21,22 @@ def ulp_diff(a, b):
 
 
 class DPCases:
-    """tests/golden/dp_cases.npz, produced from the reference by make_golden.py."""
+    """tests/golden/dp_cases_*.npz, produced from the reference by make_golden.py: whole cases
+    per part (each part under the size limit for a committed file), n_cases in every part."""
 
     def __init__(self):
-        self.d = np.load(os.path.join(GOLDEN, "dp_cases.npz"))
-        self.n = int(self.d["n_cases"])
+        import glob
+
+        self.parts = [np.load(f) for f in sorted(glob.glob(os.path.join(GOLDEN, "dp_cases_*.npz")))]
+        self.n = int(self.parts[0]["n_cases"])
+        assert {k[:4] for d in self.parts for k in d.files if k != "n_cases"} == {f"c{i:03d}" for i in range(self.n)}
 
     def __len__(self):
         return self.n
 
     def __getitem__(self, i):
         p = f"c{i:03d}_"
-        return {k[len(p):]: self.d[k] for k in self.d.files if k.startswith(p)}
+        return {k[len(p):]: d[k] for d in self.parts for k in d.files if k.startswith(p)}
 
 
 @pytest.fixture(scope="session")

@@ -6,7 +6,7 @@ never imported by the package or by the tests.  It imports the *reference* whisp
 image lacks (torchaudio, nltk, pyannote), runs the reference functions on seeded
 synthetic inputs and writes only their inputs/outputs as fixtures:
 
-  dp_cases.npz      get_trellis / backtrack / merge_repeats     (alignment.py:359-454)
+  dp_cases_*.npz    get_trellis / backtrack / merge_repeats     (alignment.py:359-454)
   align_cases.npz   align() end to end with a fake CTC model    (alignment.py:100-354)
   align_cases.json  expected align() outputs
   vad_cases.npz     Binarize / merge_chunks                     (vad.py:61-195, 264-311)
@@ -209,6 +209,9 @@ def dp_reference(A, em, toks, blank):
     return tr.numpy(), tstart, path
 
 
+DP_PARTS = [(0, 20), (21, 27), (28, 30)]  # first and last case of each dp_cases_<part>.npz
+
+
 def build_dp_cases(A):
     rng = np.random.default_rng(1234)
     cases = []
@@ -266,9 +269,11 @@ def build_dp_cases(A):
         c["trellis_rowT"] = tr[-1, :].copy()
         for k, v in c.items():
             cases.append((f"c{ci:03d}_{k}", v))
-    arrays = dict(cases)
-    arrays["n_cases"] = np.int64(len(specs))
-    np.savez_compressed(os.path.join(OUT, "dp_cases.npz"), **arrays)
+    # whole cases per part, each part under the 1 MiB limit for a committed file
+    for part, (lo, hi) in enumerate(DP_PARTS):
+        arrays = {k: v for k, v in cases if lo <= int(k[1:4]) <= hi}
+        arrays["n_cases"] = np.int64(len(specs))
+        np.savez_compressed(os.path.join(OUT, f"dp_cases_{part}.npz"), **arrays)
     print("dp cases:", len(specs))
 
 

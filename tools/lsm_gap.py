@@ -63,7 +63,11 @@ def cases_cfg(rng, S, T, V, n_lo, n_hi):
 
 
 def golden_cases():
-    d = np.load(os.path.join(ROOT, "tests", "golden", "dp_cases.npz"), allow_pickle=False)
+    import glob
+
+    d = {}
+    for f in sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "dp_cases_*.npz"))):
+        d.update(np.load(f, allow_pickle=False))
     ids = sorted({k.split("_")[0] for k in d.keys() if k.endswith("_em")})
     return [(d[f"{i}_em"].astype(np.float32), d[f"{i}_tokens"], int(d[f"{i}_blank"])) for i in ids]
 

@@ -9,7 +9,7 @@
 #       counter group per run, rocprofv3 does not split groups); then the kernel stats of the VAD
 #       producer over 1 h (vad1h) and of align() end to end (e2e); condensed by
 #       tools/summarize_profiles.py into gpurun_out/profiles_ROUND/ (raw traces deleted: gpurun
-#       brings back <= 64 MiB), and the default bench line into gpurun_out/ROUND_bench.log.
+#       brings back <= 64 MiB), and the `bench.py --full` line, printed last (log: $TMPDIR/ROUND_bench.log).
 #   tools/profile_round.sh sat-ab VARIANT...
 #       saturated-kernel variants built by tools/build_variant.sh (build/libt_VARIANT.so): kernel
 #       stats of tools/legs.py sat3000 and one PMC pass for the effective clock
@@ -60,8 +60,8 @@ case $MODE in
       find "gpurun_out/prof_$RND/$LEG/stats" -name "*kernel_stats.csv" -exec cp {} "gpurun_out/profiles_$RND/${RND}_${LEG}_kernel_stats.csv" \;
     done
     rm -rf "gpurun_out/prof_$RND"
-    timeout -k 10 600 python3 bench.py > "gpurun_out/${RND}_bench.log" 2>&1 || { echo "bench failed"; tail -20 "gpurun_out/${RND}_bench.log"; exit 1; }
-    tail -n 1 "gpurun_out/${RND}_bench.log" | cut -c1-400
+    timeout -k 10 600 python3 bench.py --full > "$TMPDIR/${RND}_bench.log" 2>&1 || { echo "bench failed"; tail -20 "$TMPDIR/${RND}_bench.log"; exit 1; }
+    tail -n 1 "$TMPDIR/${RND}_bench.log" | cut -c1-400
     ;;
   sat-ab)
     cd "$R"
