@@ -23,6 +23,8 @@
  *                        segmentation overlap-add (pyannote Inference.aggregate)
  *   wx_sincnet_stage  <- whisperx/vad.py:198-240 (the segmentation model's SincNet stages:
  *                        |.| / max-pool / instance norm / leaky ReLU, fused)
+ *   wx_assign_speakers <- whisperx/diarize.py:35-67  assign_word_speakers(diarize_df,
+ *                        transcript_result, fill_nearest), every segment and word of a corpus
  *
  * Conventions
  *   - All data pointers are DEVICE pointers (allocated by the caller; the library never
@@ -340,6 +342,33 @@ int wx_lstm_bidir_layer(const float* xp, const float* whh, float* y, int64_t B, 
 int wx_vad_aggregate(const float* scores, const int64_t* start_frame, int32_t n_chunks,
                      int32_t frames_per_chunk, int32_t n_classes, int64_t n_frames, float missing,
                      float* out, void* stream);
+
+/* assign_word_speakers (diarize.py:35-67), batched over F files in one launch: for every
+ * query (qs, qe) — a segment or a timed word — the speaker whose diarization turns overlap it
+ * most.  All times fp64.
+ *   Turns of file f are grouped by speaker: its groups are grp_off[f] .. grp_off[f + 1] (in
+ *   sorted label order, so a group's index within the file is the speaker's rank), group g
+ *   owns turns turn_off[g] .. turn_off[g + 1] of turn_start / turn_end, in the table's row
+ *   order (the caller stable-sorts the table by speaker rank).  G = grp_off[F] groups and
+ *   n_turns = turn_off[G] turns in all (host values; turn_start / turn_end may be NULL when
+ *   n_turns == 0).  Queries of file f are q_off[f] .. q_off[f + 1] of q_start / q_end,
+ *   Q = q_off[F].
+ *   Per query and turn x = min(end, qe) - max(start, qs) (NaN-propagating, as numpy's).  With
+ *   fill_nearest == 0 the turns with x > 0 take part; otherwise every turn does, a NaN x
+ *   adding nothing.  A speaker's sum runs over its participating turns in row order with Kahan
+ *   compensation (y = x - c; t = s + y; c = (t - s) - y; s = t — pandas' groupby().sum()),
+ *   and exists once one turn takes part.  speaker[q] = the rank of the largest sum, the
+ *   lowest rank among equal sums (a NaN sum only when there is no other), or -1 when no
+ *   speaker has a sum; best_sum[q] (may be NULL) = that sum, 0.0 with -1.  Non-finite times
+ *   follow plain IEEE arithmetic in the recurrence.
+ * Only enqueues on `stream`; no workspace.  Null pointers or negative sizes: WX_E_INVALID.
+ * F == 0 or Q == 0: WX_OK without a launch.  Nothing outside speaker / best_sum [0, Q) is
+ * written. */
+int wx_assign_speakers(const double* turn_start, const double* turn_end, const int64_t* turn_off,
+                       const int64_t* grp_off, int64_t G, int64_t n_turns,
+                       const double* q_start, const double* q_end, const int64_t* q_off,
+                       int32_t F, int64_t Q, int32_t fill_nearest,
+                       int32_t* speaker, double* best_sum, void* stream);
 
 #ifdef __cplusplus
 }

@@ -21,7 +21,8 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("WX_LIB_PATH") or os.path.join(_HERE, "libwxalign.so")
 SRC_PATH = os.path.join(_HERE, "csrc", "wx_align.hip")
-SRC_PATHS = [SRC_PATH, os.path.join(_HERE, "csrc", "wx_emission.hip"), os.path.join(_HERE, "csrc", "wx_vad.hip")]
+SRC_PATHS = [SRC_PATH, os.path.join(_HERE, "csrc", "wx_emission.hip"), os.path.join(_HERE, "csrc", "wx_vad.hip"),
+             os.path.join(_HERE, "csrc", "wx_diarize.hip")]
 INST_PATH = os.path.join(_HERE, "csrc", "wx_align_inst.hip")
 HDR_PATHS = [os.path.join(_HERE, "csrc", "wx_align_dp.h"), INST_PATH]
 INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
@@ -97,6 +98,8 @@ SIGNATURES = {
                                       _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wx_binarize_plan": (ctypes.c_int, [_f32, _f32, _i64, ctypes.c_char_p, _sz]),
     "wx_sincnet_stage": (ctypes.c_int, [_vp, _i64, _i64, _i32, _i64, _i32, _vp, _vp, _f32, _f32, _vp, _vp]),
+    "wx_assign_speakers": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i32, _i64, _i32,
+                                          _vp, _vp, _vp]),
 }
 
 
@@ -558,6 +561,77 @@ def vad_aggregate(scores: torch.Tensor, start_frames, n_frames: int, missing: fl
         _check(lib.wx_vad_aggregate(_ptr(sc), _ptr(sf), n_chunks, K, n_cls, int(n_frames), float(missing),
                                     _ptr(out), _stream(dev)))
     return out[: int(n_frames)]
+
+
+class SpeakerTurns:
+    """Diarization turn tables of F files packed for wx_assign_speakers (host arrays, numpy
+    only: the host route of whisperx_amd.diarize walks the same packing).  Per file the
+    speakers are ranked by sorted label order (pandas' groupby order) and the turns
+    stable-sorted by rank, so a group holds one speaker's turns in table row order:
+    start / end [n_turns] fp64, turn_off [G + 1], grp_off [F + 1] int64, labels[f] = the
+    file's labels by rank."""
+
+    def __init__(self, tables):
+        starts, ends, turn_off, grp_off, self.labels = [], [], [0], [0], []
+        for start, end, speaker in tables:
+            start = np.asarray(start, dtype=np.float64).reshape(-1)
+            end = np.asarray(end, dtype=np.float64).reshape(-1)
+            speaker = list(speaker)
+            if not (len(start) == len(end) == len(speaker)):
+                raise ValueError("a turn table's start, end and speaker columns differ in length")
+            labels = sorted(set(speaker))
+            rank_of = {s: r for r, s in enumerate(labels)}
+            rank = np.fromiter((rank_of[s] for s in speaker), dtype=np.int64, count=len(speaker))
+            order = np.argsort(rank, kind="stable")
+            starts.append(start[order])
+            ends.append(end[order])
+            counts = np.bincount(rank, minlength=len(labels))
+            for n in counts:
+                turn_off.append(turn_off[-1] + int(n))
+            grp_off.append(grp_off[-1] + len(labels))
+            self.labels.append(labels)
+        self.F = len(self.labels)
+        self.start = np.concatenate(starts) if starts else np.zeros(0)
+        self.end = np.concatenate(ends) if ends else np.zeros(0)
+        self.turn_off = np.asarray(turn_off, dtype=np.int64)
+        self.grp_off = np.asarray(grp_off, dtype=np.int64)
+        self.G = int(self.grp_off[-1])
+        self.n_turns = int(self.turn_off[-1])
+
+
+def assign_speakers(turns: SpeakerTurns, q_start, q_end, q_off, fill_nearest: bool = False, device=None,
+                    speaker_out: Optional[torch.Tensor] = None, best_out: Optional[torch.Tensor] = None):
+    """wx_assign_speakers over packed turns and queries (q_start / q_end [Q] fp64 host arrays,
+    q_off [F + 1]): one launch on the current stream.  Returns device tensors (speaker [Q]
+    int32: rank within the file or -1; best_sum [Q] fp64).  speaker_out / best_out: contiguous
+    device tensors of Q elements to write into instead of fresh ones."""
+    lib = load()
+    dev = torch.device(device) if device is not None else torch.device("cuda")
+    if dev.type != "cuda":
+        raise WXError(f"assign_speakers: {dev} is not a HIP device")
+    if dev.index is None:  # "cuda": the current device, spelled as tensors report it
+        dev = torch.device("cuda", torch.cuda.current_device())
+    q_start = np.ascontiguousarray(q_start, dtype=np.float64).reshape(-1)
+    q_end = np.ascontiguousarray(q_end, dtype=np.float64).reshape(-1)
+    q_off = np.ascontiguousarray(q_off, dtype=np.int64).reshape(-1)
+    Q, F, nt = int(q_start.size), turns.F, turns.n_turns
+    if q_end.size != Q or q_off.size != F + 1 or int(q_off[0]) != 0 or int(q_off[-1]) != Q or np.any(np.diff(q_off) < 0):
+        raise WXError("assign_speakers: q_off must be F + 1 non-decreasing offsets from 0 to len(q_start) == len(q_end)")
+    speaker = speaker_out if speaker_out is not None else torch.empty(max(Q, 1), dtype=torch.int32, device=dev)[:Q]
+    best = best_out if best_out is not None else torch.empty(max(Q, 1), dtype=torch.float64, device=dev)[:Q]
+    for t, dt in ((speaker, torch.int32), (best, torch.float64)):
+        if t.dtype != dt or t.numel() != Q or not t.is_contiguous() or t.device != dev:
+            raise WXError("assign_speakers: outputs must be contiguous int32 / float64 device tensors of Q elements")
+    # two uploads: the fp64 arrays and the int64 tables, each through one pinned buffer; both
+    # stay referenced until the launch is enqueued
+    f64 = _h2d(np.concatenate([turns.start, turns.end, q_start, q_end, np.zeros(1)]), torch.float64, dev)
+    i64 = _h2d(np.concatenate([turns.turn_off, turns.grp_off, q_off]), torch.int64, dev)
+    n_to, n_go = turns.turn_off.size, turns.grp_off.size
+    with torch.cuda.device(dev):
+        _check(lib.wx_assign_speakers(_ptr(f64[0:]), _ptr(f64[nt:]), _ptr(i64[0:]), _ptr(i64[n_to:]), turns.G, nt,
+                                      _ptr(f64[2 * nt:]), _ptr(f64[2 * nt + Q:]), _ptr(i64[n_to + n_go:]), F, Q,
+                                      int(bool(fill_nearest)), _ptr(speaker), _ptr(best), _stream(dev)))
+    return speaker, best
 
 
 def sincnet_stage(x_tm: torch.Tensor, do_abs: bool, gamma, beta, eps: float, slope: float = 0.01,
