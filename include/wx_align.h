@@ -25,6 +25,8 @@
  *                        |.| / max-pool / instance norm / leaky ReLU, fused)
  *   wx_assign_speakers <- whisperx/diarize.py:35-67  assign_word_speakers(diarize_df,
  *                        transcript_result, fill_nearest), every segment and word of a corpus
+ *   wx_log_mel        <- whisperx/audio.py:140-159  log_mel_spectrogram(audio, n_mels, padding),
+ *                        every VAD chunk of a file (asr.py:141-149 preprocess) in one launch
  *
  * Conventions
  *   - All data pointers are DEVICE pointers (allocated by the caller; the library never
@@ -369,6 +371,45 @@ int wx_assign_speakers(const double* turn_start, const double* turn_end, const i
                        const double* q_start, const double* q_end, const int64_t* q_off,
                        int32_t F, int64_t Q, int32_t fill_nearest,
                        int32_t* speaker, double* best_sum, void* stream);
+
+/* log_mel_spectrogram (audio.py:140-159), batched over B chunks of one waveform: for chunk b,
+ * what the reference returns for log_mel_spectrogram(wave[first : first + len], n_mels, pad).
+ *     audio = F.pad(audio, (0, padding))                                      (audio.py:148)
+ *     stft = torch.stft(audio, N_FFT, HOP_LENGTH, window=hann_window(N_FFT))  (:149-150)
+ *     magnitudes = stft[..., :-1].abs() ** 2                                  (:151)
+ *     mel_spec = filters @ magnitudes                                         (:153-154)
+ *     log_spec = clamp(mel_spec, min=1e-10).log10()                           (:156)
+ *     log_spec = maximum(log_spec, log_spec.max() - 8.0)                      (:157)
+ *     log_spec = (log_spec + 4.0) / 4.0                                       (:158)
+ *   The signal is the chunk followed by `pad` zeros, L = len + pad samples; torch.stft's
+ *   center=True reflect extension by 200 samples on both sides is taken of that padded signal;
+ *   frames 0 .. L / 160 - 1 (the last STFT frame is dropped); the maximum is the chunk's own.
+ *   wave: n_wave fp32 samples on the device (4-byte alignment suffices; chunks may start
+ *   anywhere).  chunk_first / chunk_len / chunk_pad: HOST arrays of B int64 (validated, and the
+ *   grid is sized from them, before anything is enqueued); chunks_dev: the same 3 B values on
+ *   the device, [3][B] (all firsts, all lengths, all paddings).
+ *   n_mels: 80 or 128.  filters: device [n_mels][201] fp32 (the Slaney mel filterbank).
+ *   basis: device, the windowed DFT basis packed as v_mfma_f32_16x16x4_f32 A fragments,
+ *   [13 bin tiles][2: cos, sin][25 tap groups][64 lanes][4] fp32 (16-byte aligned): entry
+ *   [bt][cs][g][lane][j] = hann(n) * (cs ? sin : cos)(2 pi k n / 400), n = 16 g + 4 (lane / 16)
+ *   + j, k = 16 bt + lane % 16, hann(n) = 0.5 - 0.5 cos(2 pi n / 400); 0 for k > 200.
+ *   out: chunk b, mel row m at out + (b n_mels + m) row_stride, frames 0 .. L_b / 160 - 1
+ *   (L_b / 160 <= n_frames_max <= row_stride; nothing else is written; 4-byte alignment
+ *   suffices).  workspace: wx_log_mel_workspace_bytes(B) bytes; after the call it holds the
+ *   per-chunk maxima of the log10 values as order-preserving uint32 keys.
+ * Two launches on `stream`: the fused frame gather / DFT / power / mel / log10 kernel (f32 MFMA:
+ * equal to the reference to fp32 tolerance, not bit-identical), which leaves each chunk's
+ * maximum in the workspace, and the floor + affine pass.  A block of 64 frames that lies wholly
+ * in the zero padding skips the GEMMs (identical values; WX_NO_MEL_SKIP=1 in the environment
+ * computes them).  Non-finite samples are out of scope.
+ * B < 0, another n_mels, a chunk outside the waveform, L_b <= 200 (torch's reflect padding
+ * refuses it too), L_b / 160 > n_frames_max, B > 65535 or a null pointer: WX_E_INVALID; a short
+ * workspace: WX_E_WORKSPACE; both before anything is enqueued.  B == 0: WX_OK. */
+size_t wx_log_mel_workspace_bytes(int32_t B);
+int wx_log_mel(const float* wave, int64_t n_wave, const int64_t* chunk_first, const int64_t* chunk_len,
+               const int64_t* chunk_pad, const int64_t* chunks_dev, int32_t B, int32_t n_mels,
+               const float* filters, const float* basis, float* out, int64_t n_frames_max,
+               int64_t row_stride, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -25,7 +25,22 @@ from .alignment import (  # noqa: F401
     merge_repeats,
     merge_words,
 )
-from .audio import SAMPLE_RATE, load_audio  # noqa: F401
+from .audio import (  # noqa: F401
+    CHUNK_LENGTH,
+    FRAMES_PER_SECOND,
+    HOP_LENGTH,
+    N_FFT,
+    N_FRAMES,
+    N_SAMPLES,
+    N_SAMPLES_PER_TOKEN,
+    SAMPLE_RATE,
+    TOKENS_PER_SECOND,
+    load_audio,
+    log_mel_chunks,
+    log_mel_spectrogram,
+    mel_filters,
+    pad_or_trim,
+)
 from .vad import Binarize, merge_chunks  # noqa: F401
 from .diarize import assign_word_speakers, assign_word_speakers_batch  # noqa: F401
 from .writers import get_writer, format_timestamp  # noqa: F401

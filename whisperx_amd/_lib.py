@@ -22,7 +22,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("WX_LIB_PATH") or os.path.join(_HERE, "libwxalign.so")
 SRC_PATH = os.path.join(_HERE, "csrc", "wx_align.hip")
 SRC_PATHS = [SRC_PATH, os.path.join(_HERE, "csrc", "wx_emission.hip"), os.path.join(_HERE, "csrc", "wx_vad.hip"),
-             os.path.join(_HERE, "csrc", "wx_diarize.hip")]
+             os.path.join(_HERE, "csrc", "wx_diarize.hip"), os.path.join(_HERE, "csrc", "wx_mel.hip")]
 INST_PATH = os.path.join(_HERE, "csrc", "wx_align_inst.hip")
 HDR_PATHS = [os.path.join(_HERE, "csrc", "wx_align_dp.h"), INST_PATH]
 INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
@@ -100,6 +100,8 @@ SIGNATURES = {
     "wx_sincnet_stage": (ctypes.c_int, [_vp, _i64, _i64, _i32, _i64, _i32, _vp, _vp, _f32, _f32, _vp, _vp]),
     "wx_assign_speakers": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i32, _i64, _i32,
                                           _vp, _vp, _vp]),
+    "wx_log_mel_workspace_bytes": (_sz, [_i32]),
+    "wx_log_mel": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _vp, _sz, _vp]),
 }
 
 
@@ -632,6 +634,79 @@ def assign_speakers(turns: SpeakerTurns, q_start, q_end, q_off, fill_nearest: bo
                                       _ptr(f64[2 * nt:]), _ptr(f64[2 * nt + Q:]), _ptr(i64[n_to + n_go:]), F, Q,
                                       int(bool(fill_nearest)), _ptr(speaker), _ptr(best), _stream(dev)))
     return speaker, best
+
+
+MEL_BIN_TILES, MEL_TAP_GROUPS = 13, 25  # wx_log_mel's basis: [13][2][25][64][4] (include/wx_align.h)
+_mel_basis: dict = {}
+_mel_mu = threading.Lock()
+
+
+def mel_basis_host() -> np.ndarray:
+    """The windowed 400-point DFT basis packed as wx_log_mel reads it (include/wx_align.h):
+    computed in fp64 (periodic Hann window times cos / sin), rounded to fp32 once."""
+    bt, cs, g, lane, j = np.meshgrid(np.arange(MEL_BIN_TILES), np.arange(2), np.arange(MEL_TAP_GROUPS), np.arange(64),
+                                     np.arange(4), indexing="ij")
+    n = 16 * g + 4 * (lane // 16) + j
+    k = 16 * bt + lane % 16
+    ang = 2.0 * np.pi * ((k * n) % 400).astype(np.float64) / 400.0
+    win = 0.5 - 0.5 * np.cos(2.0 * np.pi * n.astype(np.float64) / 400.0)
+    val = win * np.where(cs == 0, np.cos(ang), np.sin(ang))
+    return np.where(k <= 200, val, 0.0).astype(np.float32)
+
+
+def mel_basis(device) -> torch.Tensor:
+    """mel_basis_host() on `device`, uploaded once per device."""
+    key = str(torch.device(device))
+    with _mel_mu:
+        t = _mel_basis.get(key)
+        if t is None:
+            t = _mel_basis[key] = torch.from_numpy(mel_basis_host()).to(device).contiguous()
+        return t
+
+
+def log_mel(wave: torch.Tensor, first, length, pad, filters: torch.Tensor, out: Optional[torch.Tensor] = None,
+            n_frames_max: Optional[int] = None) -> torch.Tensor:
+    """wx_log_mel: the reference's log_mel_spectrogram(wave[first : first + length], n_mels, pad)
+    for every chunk (first / length / pad: host int sequences of B entries) of a 1-D fp32 device
+    waveform, on the current stream.  filters: [n_mels, 201] fp32 on the same device.  Returns
+    `out`, a [B, n_mels, n_frames_max] fp32 device tensor (made here unless given: any batch
+    stride that is a multiple of n_mels rows, any row stride, last dim contiguous); chunk b fills
+    frames 0 .. (length + pad) // 160 - 1 of its rows and nothing else."""
+    lib = load()
+    if wave.dim() != 1 or wave.dtype != torch.float32 or not wave.is_cuda or not wave.is_contiguous():
+        raise WXError("log_mel: wave must be a contiguous 1-D float32 device tensor")
+    dev = wave.device
+    ch = np.ascontiguousarray(np.stack([np.asarray(first, dtype=np.int64).reshape(-1),
+                                        np.asarray(length, dtype=np.int64).reshape(-1),
+                                        np.asarray(pad, dtype=np.int64).reshape(-1)]))
+    B = int(ch.shape[1])
+    n_mels = int(filters.shape[0])
+    if tuple(filters.shape) != (n_mels, 201) or filters.dtype != torch.float32 or filters.device != dev \
+            or not filters.is_contiguous():
+        raise WXError("log_mel: filters must be a contiguous [n_mels, 201] float32 tensor on the waveform's device")
+    frames = int(((ch[1] + ch[2]) // 160).max()) if B else 0
+    if n_frames_max is None:
+        n_frames_max = int(out.shape[2]) if out is not None else frames
+    if out is None:
+        out = torch.empty((B, n_mels, n_frames_max), dtype=torch.float32, device=dev)
+    if out.dim() != 3 or tuple(out.shape[:2]) != (B, n_mels) or out.shape[2] < n_frames_max or out.dtype != torch.float32 \
+            or out.device != dev or (out.shape[2] > 1 and out.stride(2) != 1) \
+            or (B > 1 and out.stride(0) != n_mels * out.stride(1)):
+        raise WXError("log_mel: out must be a float32 [B, n_mels, >= n_frames_max] device tensor with contiguous frames "
+                      "and chunks n_mels rows apart")
+    if B == 0:
+        return out
+    basis = mel_basis(dev)
+    chunks_d = _dev_i64(ch.reshape(-1), dev)  # referenced until the launches are enqueued
+    wsb = lib.wx_log_mel_workspace_bytes(B)
+    host = [ctypes.c_void_p(ch[i].ctypes.data) for i in range(3)]  # (ch stays referenced through the call)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        ws = _ws_emit.get(f"mel/{dev}/{stream.cuda_stream}", wsb, dev)
+        _check(lib.wx_log_mel(_ptr(wave), int(wave.numel()), host[0], host[1], host[2], _ptr(chunks_d), B,
+                              n_mels, _ptr(filters), _ptr(basis), _ptr(out), int(n_frames_max), int(out.stride(1)), _ptr(ws), wsb,
+                              ctypes.c_void_p(stream.cuda_stream)))
+    return out
 
 
 def sincnet_stage(x_tm: torch.Tensor, do_abs: bool, gamma, beta, eps: float, slope: float = 0.01,

@@ -6,6 +6,7 @@ The reference binds the alignment/VAD names at import time in several modules, s
   whisperx/__init__.py:2    from .alignment import load_align_model, align
   whisperx/transcribe.py:9  from .alignment import align, load_align_model   (CLI, :188,:201,:203)
   whisperx/asr.py:13        from .vad import load_vad_model, merge_chunks      (:187, :347)
+  whisperx/asr.py:12        from .audio import ... log_mel_spectrogram         (:144, :249)
   whisperx/transcribe.py:13 from .utils import ... get_writer ...
   whisperx/__init__.py:4    from .diarize import assign_word_speakers, DiarizationPipeline
   whisperx/transcribe.py:12 from .diarize import DiarizationPipeline, assign_word_speakers   (:222)
@@ -56,7 +57,7 @@ def _vad_loader(reference_loader):
 
 
 def _targets() -> Dict[str, Dict[str, object]]:
-    from . import alignment, diarize, vad, writers
+    from . import alignment, audio, diarize, vad, writers
 
     align_names = {n: getattr(alignment, n) for n in
                    ("align", "load_align_model", "get_trellis", "backtrack", "merge_repeats", "merge_words",
@@ -67,7 +68,9 @@ def _targets() -> Dict[str, Dict[str, object]]:
         "alignment": align_names,
         "transcribe": {"align": alignment.align, "load_align_model": alignment.load_align_model,
                        "get_writer": writers.get_writer, "assign_word_speakers": diarize.assign_word_speakers},
-        "asr": {"merge_chunks": vad.merge_chunks, "load_vad_model": _vad_loader},
+        "asr": {"merge_chunks": vad.merge_chunks, "load_vad_model": _vad_loader,
+                "log_mel_spectrogram": audio.drop_in_log_mel_spectrogram},
+        "audio": {"log_mel_spectrogram": audio.drop_in_log_mel_spectrogram},
         "vad": {"merge_chunks": vad.merge_chunks, "Binarize": vad.Binarize, "load_vad_model": _vad_loader},
         "utils": {"get_writer": writers.get_writer},
         # (whisperx.diarize imports pyannote.audio: without it the module is skipped)

@@ -6,6 +6,9 @@ wav2vec2 checkpoints.  Everything below is shaped like the real inputs, never th
   summing to 10 h.
 * ``vad_scores``: a file's VAD scores, smoothed Gaussian noise through a sigmoid, on the
   pyannote segmentation model's frame geometry (16.875 ms step, 61.9375 ms window).
+* ``waveform`` / ``vad_chunks``: an hour of speech-shaped noise (bursts at varying levels over
+  a faint background) and merge_chunks-like chunks of 15-30 s at non-aligned offsets, for the
+  feature benchmark (tools/mel_bench.py).
 * ``Transcriber``: the ASR stage's output stand-in, random lower-case words at ~14 chars/s
   for each VAD chunk, with the chunk bounds rounded to 3 decimals as asr.py:226-232 does.
 * ``SyntheticCTC``: a cheap, deterministic CTC "model" with wav2vec2's frame geometry and
@@ -72,6 +75,35 @@ def vad_scores(seed: int, duration_s: float):
     y = np.convolve(x, np.ones(40) / 40, mode="valid")[:F] * 4 * np.sqrt(40) / 3
     data = (1 / (1 + np.exp(-y))).astype(np.float32)[:, None]
     return SlidingWindowFeature(data, SlidingWindow(start=0.0, duration=VAD_DURATION, step=VAD_STEP))
+
+
+def waveform(seed: int, duration_s: float) -> np.ndarray:
+    """[duration * 16000] fp32 samples shaped like speech levels: Gaussian noise under an
+    envelope of 0.2-1.5 s bursts (levels log-uniform over 30 dB) separated by 0.05-0.8 s of
+    faint background noise (-60 dB)."""
+    rng = np.random.default_rng(seed)
+    n = int(round(duration_s * 16000))
+    env = np.full(n, 1e-3, dtype=np.float32)
+    t = 0
+    while t < n:
+        burst = int(rng.uniform(0.2, 1.5) * 16000)
+        env[t:t + burst] = 0.3 * 10.0 ** (-1.5 * rng.random())
+        t += burst + int(rng.uniform(0.05, 0.8) * 16000)
+    out = rng.standard_normal(n, dtype=np.float32)
+    out *= env
+    return out
+
+
+def vad_chunks(seed: int, duration_s: float, lo_s: float = 15.0, hi_s: float = 30.0):
+    """merge_chunks-like chunks ({'start', 'end'} in seconds, vad.py:264-307) covering a file:
+    lengths uniform in [lo_s, hi_s], gaps of 0.2-2 s, bounds at no particular sample alignment."""
+    rng = np.random.default_rng(seed)
+    out, t = [], float(rng.uniform(0.0, 1.0))
+    while t + lo_s < duration_s:
+        end = min(t + float(rng.uniform(lo_s, hi_s)), duration_s)
+        out.append({"start": t, "end": end, "segments": [(t, end)]})
+        t = end + float(rng.uniform(0.2, 2.0))
+    return out
 
 
 class Transcriber:
