@@ -114,14 +114,9 @@ __device__ __forceinline__ unsigned long long readlane64(unsigned long long x, i
 // in row order onto S(t0) and nothing else — the sequential chain's additions exactly.  (Round
 // 5: two instructions per row instead of a conversion, a DPP shift and the add; config 2 50.8
 // -> 47.5 us.)
-__device__ __forceinline__ double col0_chain(double acc, float e) {
-    const int l = lane_id();
-    __shared__ __attribute__((aligned(16))) double c0d[kChunk];
-    if (l < kChunk) c0d[l] = (double)e;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (other lanes' writes, read below)
-    double dv[kChunk];
-#pragma unroll
-    for (int j = 0; j < kChunk; ++j) dv[j] = c0d[j];
+// col0_run: the chain alone, on the chunk's 32 doubles already broadcast into registers (the
+// register-resident forward's column-0 helper reads the next chunk's while it waits: col0_helper).
+__device__ __forceinline__ double col0_run(double acc, const double (&dv)[kChunk]) {
     double a = acc;
     unsigned long long sv;
 #define WX_C0_STEP(J, BIT) "v_add_f64 %[a], %[a], %[d" #J "]\n\ts_bitset0_b64 exec, " #BIT "\n\t"
@@ -144,6 +139,16 @@ __device__ __forceinline__ double col0_chain(double acc, float e) {
 #undef WX_C0_BLOCK
 #undef WX_C0_STEP
     return a;
+}
+__device__ __forceinline__ double col0_chain(double acc, float e) {
+    const int l = lane_id();
+    __shared__ __attribute__((aligned(16))) double c0d[kChunk];
+    if (l < kChunk) c0d[l] = (double)e;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (other lanes' writes, read below)
+    double dv[kChunk];
+#pragma unroll
+    for (int j = 0; j < kChunk; ++j) dv[j] = c0d[j];
+    return col0_run(acc, dv);
 }
 
 // One chunk of column 0's running sum: lane l (0..31) holds e = em[t0 + l, 0] (lanes 32..63:
@@ -1090,22 +1095,102 @@ struct Forward {
                 st_pub4<kWT>(cn, t0 + 4 * i, make_float4(hist[4 * i], hist[4 * i + 1], hist[4 * i + 2], hist[4 * i + 3]));
         }
     }
-    // tr[t][0] + em[t, tok[0]] for the rows of chunk q (the column-1 wave's lane-0 operand),
-    // into column VS of the chunk's quad buffer.  tr[t][0] (alignment.py:367-370): 0 at t = 0,
-    // fp32 of the fp64 sum of em[0..t-1, 0] (torch CPU cumsum accumulates in double, in row
-    // order), +inf in the last N rows.  The sums: col0_chunk.
-    __device__ __forceinline__ static void col0_pre(int q, const SegDesc& d, float* buf, int tok0, double& acc) {
+    // Part 0's column-0 helper (wave W + 1 of a register-resident split kernel): col0_pre, the
+    // column-1 wave's lane-0 operand tr[t][0] + em[t, tok[0]], for the rows of every chunk, into
+    // column VS of the chunk's quad buffer.  tr[t][0] (alignment.py:367-370): 0 at t = 0, fp32 of
+    // the fp64 sum of em[0..t-1, 0] (torch CPU cumsum accumulates in double, in row order), +inf
+    // in the last N rows.  Barriers as helper_reg: -1, then col0_pre of chunks 0 and 1, then one
+    // barrier per chunk q followed by col0_pre of chunk q + 2, due before barrier q + 1.
+    // Pipelined so that what stands between two barriers is the fp64 chain and the 32 stores,
+    // not the LDS round trips around them (row reads, conversion, the write and the 16
+    // broadcast reads of col0_chain: ~1.3k cycles per chunk, which made this wave the last one
+    // at every barrier of part 0): the two columns come straight from the emission rows, loaded
+    // four chunks ahead (unconditional, clamped — the quad buffers and the stager are not
+    // involved), and chunk c + 1's doubles are converted, written to the other half of c0d and
+    // read back broadcast after chunk c's chain and stores, on the way to the next barrier.
+    // The additions and their order are col0_chain's: col0_run on the same 32 doubles.
+    struct C0Rows {
+        float e, et;  // em[t, 0], em[t, tok[0]] of row 32 c + (lane & 31)
+    };
+    __device__ static void col0_helper(const SegDesc& d, const float* __restrict__ E, int V, float* lds, int nch,
+                                       int tok0) {
+        __shared__ __attribute__((aligned(16))) double c0d[2][kChunk];
         const int T = d.T, N = d.N;
-        const int l = lane_id();
-        const int rr = l & 31;
-        // both operands of the row read up front: one LDS round trip instead of two
-        const float e = buf[(rr >> 2) * kQS + (rr & 3)];              // em[t, 0]
-        const float et = buf[(rr >> 2) * kQS + 4 * tok0 + (rr & 3)];  // em[t, tok[0]]
-        const double a = col0_chunk(acc, e);
-        if (l < 32) {
-            const int t = q * kChunk + l;
-            buf[(l >> 2) * kQS + 4 * VS + (l & 3)] = col0_value(t, a, T, N) + et;
+        const int l = lane_id(), rr = l & 31;
+        auto load = [&](C0Rows& r, int c) {
+            const float* row = E + (int64_t)min(c * kChunk + rr, T - 1) * V;
+            r.e = row[0];
+            r.et = row[tok0];
+        };
+        auto bcast = [&](int h, double(&dv)[kChunk]) {
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (other lanes' writes, read below)
+#pragma unroll
+            for (int j = 0; j < kChunk; ++j) dv[j] = c0d[h][j];
+        };
+        C0Rows r0, r1, r2, r3;
+        load(r0, 0);
+        load(r1, 1);
+        load(r2, 2);
+        load(r3, 3);
+        double acc = 0.0;
+        double dvA[kChunk], dvB[kChunk];
+#ifdef WX_PHASE_TIMING
+        unsigned long long acc_work = 0, acc_bar = 0;
+#endif
+        __syncthreads();  // barrier -1
+        if (l < kChunk) c0d[0][l] = (double)r0.e;
+        bcast(0, dvA);
+        // chunk c: rows rc, doubles dvc; leaves chunk c + 1's doubles in dvn and reloads rc with
+        // chunk c + 4
+        auto iter = [&](const int c, C0Rows& rc, const C0Rows& rn, const double(&dvc)[kChunk], double(&dvn)[kChunk]) {
+            WX_T(h0);
+            const double a = col0_run(acc, dvc);
+            acc = __builtin_bit_cast(double, readlane64(__builtin_bit_cast(unsigned long long, a), kChunk));
+            float* buf = lds + (c % kBufs) * kBufFloats;
+            if (l < kChunk) {
+                buf[(l >> 2) * kQS + 4 * VS + (l & 3)] = col0_value(c * kChunk + l, a, T, N) + rc.et;
+                c0d[(c + 1) & 1][l] = (double)rn.e;
+            }
+            load(rc, c + 4);
+            bcast((c + 1) & 1, dvn);
+            WX_T(h1);
+#ifdef WX_PHASE_TIMING
+            acc_work += h1 - h0;
+#endif
+        };
+        auto barrier = [&]() {
+            WX_T(b0);
+            __syncthreads();
+            WX_T(b1);
+#ifdef WX_PHASE_TIMING
+            acc_bar += b1 - b0;
+#endif
+        };
+        iter(0, r0, r1, dvA, dvB);
+        if (nch > 1) iter(1, r1, r2, dvB, dvA);
+        for (int q = 0; q < nch;) {  // barrier q, then chunk q + 2 (rows slot (q + 2) % 4, doubles by parity)
+            barrier();
+            if (q + 2 < nch) iter(q + 2, r2, r3, dvA, dvB);
+            if (++q >= nch) break;
+            barrier();
+            if (q + 2 < nch) iter(q + 2, r3, r0, dvB, dvA);
+            if (++q >= nch) break;
+            barrier();
+            if (q + 2 < nch) iter(q + 2, r0, r1, dvA, dvB);
+            if (++q >= nch) break;
+            barrier();
+            if (q + 2 < nch) iter(q + 2, r1, r2, dvB, dvA);
+            ++q;
         }
+        wait_vm();  // (no load outlives the wave)
+#ifdef WX_PHASE_TIMING
+        if (l == 0 && blockIdx.x < 8192) {  // [work, barrier wait, 0]
+            unsigned long long* o = wx_loop + ((size_t)blockIdx.x * kLoopSlots + W + 1) * 3;
+            o[0] = acc_work;
+            o[1] = acc_bar;
+            o[2] = 0;
+        }
+#endif
     }
     // Staging of the quad layout.  Rows are first copied row-major into a ring of kRing raw
     // chunk buffers by 16-byte LDS-DMA (stage_rows: 4 instructions per chunk when V == 32,
@@ -1134,12 +1219,12 @@ struct Forward {
     }
     // The two helpers of a register-resident split kernel.  Barriers: -1, then one per chunk.
     // Wave W (the stager) makes chunk q + 2's quad buffer ready before barrier q (transposed
-    // out of the raw ring, its DMA issued two iterations earlier); wave W + 1 (part 0 only)
-    // writes col0_pre of chunks 0 and 1 after barrier -1 and of chunk q + 2 after barrier q.
+    // out of the raw ring, its DMA issued two iterations earlier); wave W + 1 (part 0 only:
+    // col0_helper) writes col0_pre of chunks 0 and 1 after barrier -1 and of chunk q + 2 after barrier q.
     // So after barrier q the DP waves can read chunk q + 1's operands, col0_pre included,
     // while they compute chunk q.  Quad buffer (q + 2) % kBufs (five) last held chunk q - 3,
-    // whose operand reads the DP waves waited for before chunk q - 3's steps and whose column
-    // 0 the helper read during chunk q - 5.
+    // whose operand reads the DP waves waited for before chunk q - 3's steps (the column-0
+    // helper reads no quad buffer: it writes column VS only).
     // The stager of a V == 32 batch with 16-byte aligned rows, through registers: lane l loads
     // 16 bytes (columns 4 cg .. 4 cg + 3, cg = (l >> 2) & 7) of row 8 i + 4 h + j (j = l & 3,
     // h = l >> 5) of a chunk with one global_load_dwordx4 per i (4 per chunk) and writes them
@@ -1240,6 +1325,10 @@ struct Forward {
                 return false;
             }
         }
+        if (col0 && !stage) {  // (NH == 2: the column-0 helper does nothing else)
+            col0_helper(d, E, V, lds, nch, tok0);
+            return false;
+        }
         auto buf = [&](int q) { return lds + (q % kBufs) * kBufFloats; };
         auto ring = [&](int q) { return raw + (q % kRing) * kChunk * VS; };
         auto rows_of = [&](int q) { return (q >= 0 && q < nch) ? min(kChunk, T - q * kChunk) : 0; };
@@ -1272,14 +1361,9 @@ struct Forward {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // slot 0's reads done before its reuse
             issue(kRing - 1);
         }
-        double acc = 0.0;
         uint64_t pre = 0;  // poll: chunk 1's granules (first read)
         if (poll) pre = granule_load(sp->xin + (int64_t)min(1, nch - 1) * sp->xstride + min(lane_id(), Geo::HL - 1) * C);
         __syncthreads();  // barrier -1
-        if (col0) {
-            col0_pre(0, d, buf(0), tok0, acc);
-            if (nch > 1) col0_pre(1, d, buf(1), tok0, acc);
-        }
 #ifdef WX_PHASE_TIMING
         unsigned long long acc_work = 0, acc_bar = 0, acc_vm = 0;
 #endif
@@ -1309,7 +1393,6 @@ struct Forward {
             WX_T(h1);
             __syncthreads();  // barrier q
             WX_T(h2);
-            if (col0 && q + 2 < nch) col0_pre(q + 2, d, buf(q + 2), tok0, acc);
             WX_T(h3);
 #ifdef WX_PHASE_TIMING
             acc_vm += hw - h0;
