@@ -1,6 +1,6 @@
 /*
  * wx_align.h — C ABI of the MI355X (gfx950) forced-alignment + VAD-segmentation library
- * (libwxalign.so, built from whisperx_amd/csrc/wx_align.hip).
+ * (libwxalign.so, built from whisperx_amd/csrc/: wx_align.hip and one file per other stage).
  *
  * The reference (NADOOIT/whisperX @ 2025-01-12) is pure Python; these entry points replace
  * the CPU functions on its alignment / VAD hot path, batched over many segments:

@@ -249,7 +249,7 @@ def test_align_dp_speculative_walk_trimmed_segments():
 
 def _capacity(C, W):
     """Tokens a (C cells/lane, W waves) bucket holds: waves >= 1 give ceil(32/C) lanes to the
-    chunk halo (wx_align.hip, Geometry)."""
+    chunk halo (wx_align_dp.h, Geometry)."""
     return C * (64 + (W - 1) * (64 - ((32 + C - 1) // C if W > 1 else 0)))
 
 
@@ -782,10 +782,13 @@ def _binarize_both(cols, geom, onset, offset, maxd):
 
     two = _lib.binarize(cols, geom, onset, offset, maxd, two_pass=True)
     one = _lib.binarize(cols, geom, onset, offset, maxd, two_pass=False)
+    wants = []
     for i, c in enumerate(cols):
         want = oracle.binarize(c, *geom[i], onset, offset, max_duration=maxd)
         for tag, (rs, re) in (("two-pass", two[i]), ("one-pass", one[i])):
             assert list(zip(rs.tolist(), re.tolist())) == want, (tag, i, len(c), onset, offset, maxd)
+        wants.append(want)
+    return wants  # the oracle's regions per column
 
 
 def test_binarize_dense_events_nan_and_ragged_files():
@@ -823,7 +826,14 @@ def test_binarize_dense_events_nan_and_ragged_files():
 def test_binarize_all_active_many_splits():
     """Scores above onset everywhere: one region cut at every max_duration, each cut an argmin
     over ~half the current list (block records + two partial blocks), with NaN runs and
-    constant stretches (ties go to the first frame)."""
+    constant stretches (ties go to the first frame).  On both wx_binarize_ex routes (the plan
+    is asserted): the scan with offset == onset; binarize_fsm_kernel with an offset the scores
+    never fall below (active from frame 0, split many times) and with one they fall below every
+    ~3 frames, re-activating on the next frame (at max_duration 0.02 every deactivation is
+    overridden by a split).  The oracle's region counts are pinned so that a degenerate input
+    cannot pass silently."""
+    from whisperx_amd import _lib
+
     rng = np.random.default_rng(12)
     F = 50_000
     y = (0.6 + 0.4 * rng.random(F)).astype(np.float32)
@@ -831,8 +841,15 @@ def test_binarize_all_active_many_splits():
     y[20_000:20_070] = np.nan
     y[33_333] = np.nan
     geom = [(0.0, 0.016875, 0.0619375)]
-    for maxd in (30.0, 7.3, 1.1, 0.02):
-        _binarize_both([y], geom, 0.5, 0.5, maxd)
+    scan = "void wx::binarize_scan_kernel(wx::BinScanArgs)"
+    fsm = "void wx::binarize_fsm_kernel(wx::BinarizeArgs, wx::BinWords)"
+    never = (37, 157, 1_012, 49_999)  # regions at each max_duration when nothing deactivates
+    for offset, plan, counts in ((0.5, scan, never), (0.55, fsm, never),
+                                 (0.8, fsm, (16_669, 16_669, 16_669, 49_999))):
+        assert _lib.binarize_plan(0.5, offset, F)[-1] == plan, offset
+        for maxd, n in zip((30.0, 7.3, 1.1, 0.02), counts):
+            (want,) = _binarize_both([y], geom, 0.5, offset, maxd)
+            assert len(want) == n, (offset, maxd, len(want))
 
 
 def test_binarize_and_merge_chunks_device_scores_dense():

@@ -21,10 +21,11 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("WX_LIB_PATH") or os.path.join(_HERE, "libwxalign.so")
 SRC_PATH = os.path.join(_HERE, "csrc", "wx_align.hip")
-SRC_PATHS = [SRC_PATH, os.path.join(_HERE, "csrc", "wx_emission.hip"), os.path.join(_HERE, "csrc", "wx_vad.hip"),
-             os.path.join(_HERE, "csrc", "wx_diarize.hip"), os.path.join(_HERE, "csrc", "wx_mel.hip")]
+SRC_PATHS = [SRC_PATH, os.path.join(_HERE, "csrc", "wx_binarize.hip"), os.path.join(_HERE, "csrc", "wx_emission.hip"),
+             os.path.join(_HERE, "csrc", "wx_vad.hip"), os.path.join(_HERE, "csrc", "wx_diarize.hip"),
+             os.path.join(_HERE, "csrc", "wx_mel.hip")]
 INST_PATH = os.path.join(_HERE, "csrc", "wx_align_inst.hip")
-HDR_PATHS = [os.path.join(_HERE, "csrc", "wx_align_dp.h"), INST_PATH]
+HDR_PATHS = [os.path.join(_HERE, "csrc", "wx_align_dp.h"), os.path.join(_HERE, "csrc", "wx_wave.h"), INST_PATH]
 INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 
 MAX_VOCAB = 16384

@@ -1,12 +1,13 @@
-// wx_align.hip — MI355X (gfx950 / CDNA4) kernels for WhisperX's forced-alignment DP and
-// VAD hysteresis, behind the C ABI of include/wx_align.h.
+// wx_align_dp.h — MI355X (gfx950 / CDNA4) kernel templates of WhisperX's forced-alignment DP,
+// behind the C ABI of include/wx_align.h (host side and the non-template kernels:
+// wx_align.hip; instantiations: the shards of wx_align_inst.hip).
 //
 // Reference being replaced (file:line in NADOOIT/whisperX @ 2025-01-12):
 //   get_trellis    whisperx/alignment.py:359-379     -> trellis_kernel (materialising)
-//   backtrack      whisperx/alignment.py:387-421     -> bits_from_trellis_kernel + walk
-//   merge_repeats  whisperx/alignment.py:438-454     -> merge_repeats_kernel
-//   align() DP     whisperx/alignment.py:242-250     -> align_dp_kernel (fused, no trellis)
-//   Binarize       whisperx/vad.py:118-180           -> binarize_kernel
+//   align() DP     whisperx/alignment.py:242-250     -> align_dp_kernel, align_dp_split_kernel
+//                                                       (fused, no trellis) + walk
+//   backtrack      whisperx/alignment.py:387-421     -> wx_align.hip: backtrack_kernel + walk
+//   merge_repeats  whisperx/alignment.py:438-454     -> wx_align.hip: merge_repeats_kernel
 //
 // Design:
 //   * One wave64 per segment.  The trellis recurrence is row-parallel: row t+1 depends only
@@ -46,12 +47,12 @@
 #include <mutex>
 
 #include "../../include/wx_align.h"
+#include "wx_wave.h"  // kWave, lane_id, uniform*, readlane64
 
 #define WX_VERSION "0.1.0"
 
 namespace wx {
 
-constexpr int kWave = 64;
 constexpr int kChunk = 32;  // emission rows per LDS buffer == bits per column word
 constexpr int kUnroll = 8;  // time steps per unrolled group
 constexpr int kMaxLdsFrames = 8192;  // segments up to this many frames keep walk state in LDS
@@ -86,24 +87,6 @@ __device__ __forceinline__ float dpp_shr1(float old_lane0, float v) {
     return __builtin_bit_cast(
         float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old_lane0), __builtin_bit_cast(int, v),
                                            0x138 /* wave_shr:1 */, 0xF, 0xF, false));
-}
-
-__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & (kWave - 1)); }
-
-__device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
-__device__ __forceinline__ int64_t uniform64(int64_t x) {
-    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(uint64_t)x);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((uint64_t)x >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ float uniformf(float x) {
-    return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x)));
-}
-// lane l's 64-bit value, wave-uniform (two v_readlane)
-__device__ __forceinline__ unsigned long long readlane64(unsigned long long x, int l) {
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)x, l);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(x >> 32), l);
-    return ((unsigned long long)hi << 32) | lo;
 }
 
 // Column 0's running sum over one 32-row chunk (alignment.py:366-370: torch's CPU cumsum
