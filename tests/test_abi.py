@@ -17,6 +17,26 @@ def declared_symbols():
     return sorted(set(re.findall(r"\b(wx_[a-z_0-9]+)\s*\(", txt)))
 
 
+def declared_arities():
+    """name -> parameter count of every wx_* prototype in the header: comments stripped, the
+    top-level commas of the parameter list counted, `void` (or nothing) is 0."""
+    txt = open(HEADER).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    txt = re.sub(r"//[^\n]*", "", txt)
+    out = {}
+    for m in re.finditer(r"\b(wx_[a-z_0-9]+)\s*\(", txt):
+        depth, i, commas = 1, m.end(), 0
+        while depth:
+            c = txt[i]
+            depth += (c == "(") - (c == ")")
+            commas += c == "," and depth == 1
+            i += 1
+        params = txt[m.end():i - 1].strip()
+        assert txt[i:].lstrip().startswith(";"), f"{m.group(1)}: not a prototype"
+        out[m.group(1)] = 0 if params in ("", "void") else commas + 1
+    return out
+
+
 @pytest.fixture(scope="module")
 def lib():
     from whisperx_amd import _lib
@@ -37,6 +57,47 @@ def test_library_exports_every_declared_symbol(lib):
     for s in declared_symbols():
         assert hasattr(lib, s), s
         assert s in _lib.SIGNATURES, f"{s} not bound in _lib.SIGNATURES"
+
+
+def test_bindings_have_the_declared_arity():
+    """A ctypes call with an argument too few is accepted silently and reads garbage: every
+    SIGNATURES entry lists as many argtypes as the header's prototype has parameters."""
+    from whisperx_amd import _lib
+
+    arity = declared_arities()
+    assert sorted(arity) == declared_symbols() and len(arity) >= 34
+    for name, n in arity.items():
+        assert len(_lib.SIGNATURES[name][1]) == n, name
+
+
+def _batch_attrs(b):
+    import torch
+
+    return {k: (v.dtype, tuple(v.shape), v.tolist()) if torch.is_tensor(v) else v for k, v in vars(b).items()}
+
+
+@pytest.mark.parametrize("Ts,tokens,blanks", [([5, 0, 3], [[1, 2], [], [3]], [0, 0, 6]), ([], [], [])])
+def test_batch_constructors_agree(Ts, tokens, blanks):
+    """Batch(list of emissions) and Batch.from_csr(packed matrix) build the same batch: every
+    attribute equal, tensors in dtype, shape and value (host tensors; no device, no library)."""
+    import torch
+
+    from whisperx_amd import _lib
+
+    g = torch.Generator().manual_seed(3)
+    ems = [torch.randn(T, 7, generator=g) for T in Ts]
+    a = _lib.Batch(ems, tokens, blanks, device="cpu")
+    b = _lib.Batch.from_csr(a.em, Ts, tokens, blanks)
+    A, B = _batch_attrs(a), _batch_attrs(b)
+    assert set(A) == set(B) >= {"S", "device", "V", "Ts", "Ns", "em_off", "tok_off", "sum_T", "em", "tok", "blank",
+                                "em_off_d", "tok_off_d", "min_N", "max_N"}
+    for k in A:
+        assert A[k] == B[k], k
+    assert a.S == len(Ts) and a.sum_T == sum(Ts) and a.em_off == [0] + [sum(Ts[:i + 1]) for i in range(len(Ts))]
+    assert a.V == (7 if Ts else 1) and a.tok.tolist() == ([x for t in tokens for x in t] or [0])
+    assert a.blank.tolist() == (blanks or [0]) and (a.min_N, a.max_N) == ((0, 2) if Ts else (0, 0))
+    if Ts:
+        assert torch.equal(a.em, torch.cat(ems, 0))
 
 
 def test_version_and_errors(lib):

@@ -866,3 +866,50 @@ def test_binarize_and_merge_chunks_device_scores_dense():
     regs = oracle.binarize(y, 0.0, 0.016875, 0.0619375, med, med, max_duration=30)
     want = oracle.merge_chunks_regions(regs, 30)
     assert got == want
+
+
+def test_trellis_writes_into_a_given_buffer():
+    """trellis(b, out=buf): the same values, in the caller's buffer and nowhere past them; a
+    buffer that is too short or of another dtype is refused before any launch."""
+    from whisperx_amd import _lib
+
+    b = _batch(_random_cases(np.random.default_rng(5), 3, (5, 40), (1, 20), 32))
+    flat, offs = _lib.trellis(b)
+    buf = torch.full((offs[-1] + 7,), float("nan"), dtype=torch.float32, device=DEV)
+    got, offs2 = _lib.trellis(b, out=buf)
+    assert got.data_ptr() == buf.data_ptr() and offs2 == offs
+    assert np.array_equal(buf[:offs[-1]].cpu().numpy(), flat[:offs[-1]].cpu().numpy(), equal_nan=True)
+    assert bool(torch.isnan(buf[offs[-1]:]).all())
+    for bad in (buf[:offs[-1] - 1], buf.double()):
+        with pytest.raises(_lib.WXError):
+            _lib.trellis(b, out=bad)
+
+
+# --------------------------------------------------------------------- scratch cache
+def test_scratch_cache_keys_growth_and_zero_fill():
+    """_lib.Scratch: one grow-only buffer per (tag, device, stream); zero=True buffers are all
+    zero when allocated and when grown."""
+    from whisperx_amd import _lib
+
+    sc = _lib.Scratch()
+    s1, s2 = torch.cuda.Stream(DEV), torch.cuda.Stream(DEV)
+    a = sc.get("a", DEV, 3000, s1)
+    assert a.dtype == torch.uint8 and a.is_cuda and a.numel() >= 3000
+    assert sc.get("a", DEV, 3000, s1).data_ptr() == a.data_ptr()  # same key, equal request
+    assert sc.get("a", DEV, 17, s1).data_ptr() == a.data_ptr()    # ... and a smaller one
+    with torch.cuda.stream(s1):  # stream=None is the current stream
+        assert sc.get("a", DEV, 3000).data_ptr() == a.data_ptr()
+    big = sc.get("a", DEV, a.numel() + 4096, s1)
+    assert big.numel() >= a.numel() + 4096
+    assert sc.get("a", DEV, 3000, s1).data_ptr() == big.data_ptr()  # buffers only grow
+    other_stream, other_tag = sc.get("a", DEV, 3000, s2), sc.get("b", DEV, 3000, s1)
+    ptrs = {t.data_ptr() for t in (a, big, other_stream, other_tag)}
+    assert len(ptrs) == 4  # (a is still referenced here, so nothing reuses its storage)
+    z = sc.get("z", DEV, 3000, s1, zero=True)
+    s1.synchronize()
+    assert int(z.count_nonzero()) == 0
+    with torch.cuda.stream(s1):
+        z.fill_(255)
+    z2 = sc.get("z", DEV, z.numel() + 4096, s1, zero=True)
+    s1.synchronize()
+    assert z2.numel() >= z.numel() + 4096 and int(z2.count_nonzero()) == 0

@@ -81,14 +81,10 @@ def main():
     b = _lib.Batch(ems, toks, [0] * len(ems), device=dev)
     del ems
     if a.leg == "trellis3000":
-        flat, offs = _lib.trellis(b)
-        offs_d = _lib._dev_i64(offs, dev)
-        lib = _lib.load()
+        flat, _ = _lib.trellis(b)
 
         def run():
-            _lib._check(lib.wx_trellis(_lib._ptr(b.em), _lib._ptr(b.em_off_d), b.V, _lib._ptr(b.tok),
-                                       _lib._ptr(b.tok_off_d), _lib._ptr(b.blank), b.S, b.max_N, _lib._ptr(flat),
-                                       _lib._ptr(offs_d), _lib._stream(dev)))
+            _lib.trellis(b, out=flat)
     else:
         plan = _lib.AlignPlan(b)
         run = plan.run

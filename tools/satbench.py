@@ -93,15 +93,13 @@ def child(args):
             ems, toks = make_batch(S, T, 32, lo, hi, 1234, dev)
             b = _lib.Batch(ems, toks, [0] * S, device=dev)
             del ems
-            tr, offs = _lib.trellis(b)
+            tr, _ = _lib.trellis(b)
             torch.cuda.synchronize()
             ms = []
             for _ in range(args.steps):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-                _lib.load().wx_trellis(_lib._ptr(b.em), _lib._ptr(b.em_off_d), b.V, _lib._ptr(b.tok),
-                                       _lib._ptr(b.tok_off_d), _lib._ptr(b.blank), b.S, b.max_N, _lib._ptr(tr),
-                                       _lib._ptr(_lib._dev_i64(offs, dev)), _lib._stream(dev))
+                _lib.trellis(b, out=tr)
                 e1.record()
                 torch.cuda.synchronize()
                 ms.append(e0.elapsed_time(e1))

@@ -1,7 +1,7 @@
 """ctypes binding of libwxalign.so (C ABI in include/wx_align.h).
 
-The library is the only compute path of this package: there is no CPU fallback.  If the
-shared object is missing, or no HIP device is visible, every entry point raises.
+Everything in this module needs the shared object and a HIP device: if either is missing,
+every entry point raises.  The package's host routes live in `audio`, `diarize` and `vad`.
 
 Tensors are PyTorch device tensors (torch is plumbing here: device memory and streams);
 the library sees raw device pointers, sizes and the current HIP stream.
@@ -25,7 +25,8 @@ SRC_PATHS = [SRC_PATH, os.path.join(_HERE, "csrc", "wx_binarize.hip"), os.path.j
              os.path.join(_HERE, "csrc", "wx_vad.hip"), os.path.join(_HERE, "csrc", "wx_diarize.hip"),
              os.path.join(_HERE, "csrc", "wx_mel.hip")]
 INST_PATH = os.path.join(_HERE, "csrc", "wx_align_inst.hip")
-HDR_PATHS = [os.path.join(_HERE, "csrc", "wx_align_dp.h"), os.path.join(_HERE, "csrc", "wx_wave.h"), INST_PATH]
+HDR_PATHS = [os.path.join(_HERE, "csrc", "wx_align_dp.h"), os.path.join(_HERE, "csrc", "wx_wave.h"),
+             os.path.join(_HERE, "csrc", "wx_host.h"), INST_PATH]
 INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 
 MAX_VOCAB = 16384
@@ -43,7 +44,6 @@ def status_ok(status):
 def status_summary(status) -> dict:
     """Counts of a status array: aligned, None, and the segments the in-kernel generic
     forward computed (recovered after a lost hand-off / too many columns)."""
-    import numpy as np
     st = status.cpu().numpy() if torch.is_tensor(status) else np.asarray(status)
     out = st & STATUS_MASK
     return {"aligned": int((out == 0).sum()), "none": int((out == 1).sum()),
@@ -177,7 +177,8 @@ def load(require_device: bool = True) -> ctypes.CDLL:
     """Load the HIP library.  Raises if it was not built or (by default) no GPU is visible."""
     global _lib
     if require_device and not torch.cuda.is_available():
-        raise WXError("whisperx_amd needs a HIP device (MI355X); none is visible and there is no CPU fallback")
+        raise WXError("whisperx_amd._lib needs a HIP device (MI355X) and none is visible; the host routes live in "
+                      "whisperx_amd.audio, .diarize and .vad")
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise WXError(f"{LIB_PATH} is missing: run whisperx_amd._lib.build() (hipcc, gfx950)")
@@ -225,53 +226,33 @@ def _dev_i64(x, device):
     return _h2d(x, torch.int64, device)
 
 
-class Workspace:
-    """Grow-only device scratch buffers, one per (device, stream): calls enqueued on different
-    streams (or from different threads) never share scratch, as the ABI's reentrancy allows.
-    A buffer is allocated while its stream is current, so the caching allocator orders its
-    reuse after that stream's pending kernels when it is replaced by a larger one."""
+class Scratch:
+    """Grow-only device scratch buffers, one per (tag, device, stream): every user has a tag of
+    its own, and calls enqueued on different streams (or from different threads) never share
+    scratch, as the ABI's reentrancy allows.  A buffer is allocated with its device and stream
+    current, so the caching allocator orders its reuse after that stream's pending kernels when
+    a larger one replaces it.  zero=True fills it with zeros when allocated or grown (the
+    hand-off region of split launches: it then holds only hand-off granules, and a launch never
+    matches an earlier launch's epoch, so no per-launch memset)."""
 
     def __init__(self):
         self.buf: dict = {}
         self._mu = threading.Lock()
 
-    def get(self, device, nbytes: int, stream=None) -> torch.Tensor:
+    def get(self, tag: str, device, nbytes: int, stream=None, zero: bool = False) -> torch.Tensor:
         device = torch.device(device)
         st = stream if stream is not None else torch.cuda.current_stream(device)
-        key = (str(device), int(st.cuda_stream))
+        key = (tag, str(device), int(st.cuda_stream))
         with self._mu:
             b = self.buf.get(key)
             if b is None or b.numel() < nbytes:
                 with torch.cuda.device(device), torch.cuda.stream(st):
-                    b = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
+                    b = (torch.zeros if zero else torch.empty)(max(nbytes, 1 << 16), dtype=torch.uint8, device=device)
                 self.buf[key] = b
             return b
 
 
-_ws = Workspace()
-
-
-class Handoff:
-    """Hand-off regions of split launches (wx_align_dp_ex), one per (device, stream): zeroed
-    when allocated or grown, then holding only hand-off granules (a launch never matches an
-    earlier launch's epoch), so no per-launch memset; two streams never share one
-    (concurrent launches must not)."""
-
-    def __init__(self):
-        self.buf: dict = {}
-
-    def get(self, device, stream_handle: int, nbytes: int) -> torch.Tensor:
-        key = (str(device), int(stream_handle))
-        with _handoff_mu:
-            b = self.buf.get(key)
-            if b is None or b.numel() < nbytes:
-                b = torch.zeros(max(nbytes, 1 << 16), dtype=torch.uint8, device=device)
-                self.buf[key] = b
-            return b
-
-
-_handoff_mu = threading.Lock()
-_handoff = Handoff()
+_scratch = Scratch()
 
 
 # ----------------------------------------------------------------------------------- batch
@@ -281,36 +262,17 @@ class Batch:
     def __init__(self, emissions, tokens, blank_ids, device=None):
         if len(emissions) != len(tokens) or len(tokens) != len(blank_ids):
             raise ValueError("emissions, tokens and blank_ids must have the same length")
-        self.S = len(emissions)
         device = torch.device(device) if device is not None else (
-            emissions[0].device if self.S and emissions[0].is_cuda else torch.device("cuda", torch.cuda.current_device()))
-        self.device = device
-        Ts = [int(e.shape[0]) for e in emissions]
+            emissions[0].device if emissions and emissions[0].is_cuda else torch.device("cuda", torch.cuda.current_device()))
         Vs = {int(e.shape[1]) for e in emissions if e.dim() == 2}
         if len(Vs) > 1:
             raise ValueError("all emissions of a batch must have the same vocabulary size")
-        self.V = Vs.pop() if Vs else 1
-        self.Ns = [len(t) for t in tokens]
-        self.Ts = Ts
-        self.em_off = [0]
-        for T in Ts:
-            self.em_off.append(self.em_off[-1] + T)
-        self.tok_off = [0]
-        for N in self.Ns:
-            self.tok_off.append(self.tok_off[-1] + N)
-        self.sum_T = self.em_off[-1]
-        if self.S:
-            em = torch.cat([e.to(device=device, dtype=torch.float32).reshape(-1, self.V) for e in emissions], 0)
+        V = Vs.pop() if Vs else 1
+        if emissions:
+            em = torch.cat([e.to(device=device, dtype=torch.float32).reshape(-1, V) for e in emissions], 0)
         else:
-            em = torch.empty((0, self.V), dtype=torch.float32, device=device)
-        self.em = em.contiguous()
-        flat = [int(x) for t in tokens for x in t]
-        self.tok = _h2d(flat if flat else [0], torch.int32, device)
-        self.blank = _h2d([int(b) for b in blank_ids] or [0], torch.int32, device)
-        self.em_off_d = _dev_i64(self.em_off, device)
-        self.tok_off_d = _dev_i64(self.tok_off, device)
-        self.min_N = min(self.Ns) if self.Ns else 0
-        self.max_N = max(self.Ns) if self.Ns else 0
+            em = torch.empty((0, V), dtype=torch.float32, device=device)
+        self._init(em.contiguous(), device, [e.shape[0] for e in emissions], tokens, blank_ids)
 
     @classmethod
     def from_csr(cls, em: torch.Tensor, Ts, tokens, blank_ids):
@@ -321,8 +283,14 @@ class Batch:
             raise ValueError("Ts, tokens and blank_ids must have the same length")
         if em.dim() != 2 or em.dtype != torch.float32 or not em.is_contiguous() or em.shape[0] != sum(Ts):
             raise ValueError("em must be a contiguous [sum(Ts), V] float32 tensor")
+        self._init(em, em.device, Ts, tokens, blank_ids)
+        return self
+
+    def _init(self, em: torch.Tensor, device, Ts, tokens, blank_ids):
+        """Both constructors end here: the offsets, the token / blank uploads and the N range of
+        the packed matrix `em`."""
         self.S = len(Ts)
-        self.device = em.device
+        self.device = device
         self.V = int(em.shape[1])
         self.Ts = [int(t) for t in Ts]
         self.Ns = [len(t) for t in tokens]
@@ -335,13 +303,12 @@ class Batch:
         self.sum_T = self.em_off[-1]
         self.em = em
         flat = [int(x) for t in tokens for x in t]
-        self.tok = _h2d(flat if flat else [0], torch.int32, self.device)
-        self.blank = _h2d([int(b) for b in blank_ids] or [0], torch.int32, self.device)
-        self.em_off_d = _dev_i64(self.em_off, self.device)
-        self.tok_off_d = _dev_i64(self.tok_off, self.device)
+        self.tok = _h2d(flat if flat else [0], torch.int32, device)
+        self.blank = _h2d([int(b) for b in blank_ids] or [0], torch.int32, device)
+        self.em_off_d = _dev_i64(self.em_off, device)
+        self.tok_off_d = _dev_i64(self.tok_off, device)
         self.min_N = min(self.Ns) if self.Ns else 0
         self.max_N = max(self.Ns) if self.Ns else 0
-        return self
 
 
 def _validate(b: Batch):
@@ -355,29 +322,37 @@ MODE_AUTO, MODE_THROUGHPUT, MODE_LATENCY, MODE_LATENCY_1CU = -1, 0, 1, 2
 MODE_SPLIT2, MODE_SPLIT3, MODE_SPLIT4 = 12, 13, 14  # latency shape over 2 / 3 / 4 CUs per segment
 
 
+def _dp_outputs(b: Batch):
+    """Fresh output tensors of a fused-DP call on `b`: (seg_start, seg_end, seg_score, t_start, status)."""
+    dev = b.device
+    nt = max(b.tok_off[-1], 1)
+    return (torch.empty(nt, dtype=torch.int32, device=dev), torch.empty(nt, dtype=torch.int32, device=dev),
+            torch.empty(nt, dtype=torch.float64, device=dev), torch.empty(max(b.S, 1), dtype=torch.int32, device=dev),
+            torch.empty(max(b.S, 1), dtype=torch.int32, device=dev))
+
+
+def _dp_args(b: Batch, outs, ws: torch.Tensor, wsb: int, ho: torch.Tensor, hob: int):
+    """wx_align_dp_ex's arguments up to the hand-off size; mode and stream follow."""
+    return (_ptr(b.em), _ptr(b.em_off_d), b.V, _ptr(b.tok), _ptr(b.tok_off_d), _ptr(b.blank), b.S, b.min_N, b.max_N,
+            b.sum_T, *(_ptr(t) for t in outs), _ptr(ws), wsb, _ptr(ho), hob)
+
+
 def align_dp(b: Batch, mode: int = MODE_AUTO):
     """Fused DP: returns device tensors (seg_start, seg_end, seg_score, t_start, status).
     `mode` picks the launch shape (WX_MODE_*); results are identical in every mode."""
     lib = load()
     _validate(b)
     dev = b.device
-    nt = max(b.tok_off[-1], 1)
-    seg_start = torch.empty(nt, dtype=torch.int32, device=dev)
-    seg_end = torch.empty(nt, dtype=torch.int32, device=dev)
-    seg_score = torch.empty(nt, dtype=torch.float64, device=dev)
-    t_start = torch.empty(max(b.S, 1), dtype=torch.int32, device=dev)
-    status = torch.empty(max(b.S, 1), dtype=torch.int32, device=dev)
+    outs = _dp_outputs(b)
     wsb = lib.wx_align_dp_workspace_bytes(b.S, b.sum_T, b.max_N)
     hob = lib.wx_align_dp_handoff_bytes(b.S, b.sum_T)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
-        ws = _ws.get(dev, wsb, stream)  # per (device, stream): concurrent calls never share it
-        ho = _handoff.get(dev, stream.cuda_stream, hob)
-        _check(lib.wx_align_dp_ex(_ptr(b.em), _ptr(b.em_off_d), b.V, _ptr(b.tok), _ptr(b.tok_off_d),
-                                  _ptr(b.blank), b.S, b.min_N, b.max_N, b.sum_T, _ptr(seg_start), _ptr(seg_end),
-                                  _ptr(seg_score), _ptr(t_start), _ptr(status), _ptr(ws), wsb, _ptr(ho), ho.numel(),
-                                  int(mode), ctypes.c_void_p(stream.cuda_stream)))
-    return seg_start, seg_end, seg_score, t_start, status
+        ws = _scratch.get("dp", dev, wsb, stream)
+        ho = _scratch.get("handoff", dev, hob, stream, zero=True)  # two streams never share one
+        _check(lib.wx_align_dp_ex(*_dp_args(b, outs, ws, wsb, ho, ho.numel()), int(mode),
+                                  ctypes.c_void_p(stream.cuda_stream)))
+    return outs
 
 
 class AlignPlan:
@@ -389,30 +364,19 @@ class AlignPlan:
         _validate(b)
         self.b = b
         self.mode = int(mode)
-        dev = b.device
-        nt = max(b.tok_off[-1], 1)
-        self.seg_start = torch.empty(nt, dtype=torch.int32, device=dev)
-        self.seg_end = torch.empty(nt, dtype=torch.int32, device=dev)
-        self.seg_score = torch.empty(nt, dtype=torch.float64, device=dev)
-        self.t_start = torch.empty(max(b.S, 1), dtype=torch.int32, device=dev)
-        self.status = torch.empty(max(b.S, 1), dtype=torch.int32, device=dev)
+        self.outs = self.seg_start, self.seg_end, self.seg_score, self.t_start, self.status = _dp_outputs(b)
         self.wsb = self.lib.wx_align_dp_workspace_bytes(b.S, b.sum_T, b.max_N)
-        self.ws = torch.empty(max(self.wsb, 1), dtype=torch.uint8, device=dev)
+        self.ws = torch.empty(max(self.wsb, 1), dtype=torch.uint8, device=b.device)
         # the plan's own hand-off region (zeroed once; it then holds only hand-off granules);
         # runs of one plan are serialised by the caller (one stream at a time)
-        self.hob = self.lib.wx_align_dp_handoff_bytes(b.S, b.sum_T) if hasattr(self.lib, "wx_align_dp_handoff_bytes") else 1
-        self.ho = torch.zeros(max(self.hob, 1), dtype=torch.uint8, device=dev)
-        self.args = (_ptr(b.em), _ptr(b.em_off_d), b.V, _ptr(b.tok), _ptr(b.tok_off_d), _ptr(b.blank), b.S,
-                     b.min_N, b.max_N, b.sum_T, _ptr(self.seg_start), _ptr(self.seg_end), _ptr(self.seg_score),
-                     _ptr(self.t_start), _ptr(self.status), _ptr(self.ws), self.wsb, _ptr(self.ho), self.hob)
+        self.hob = self.lib.wx_align_dp_handoff_bytes(b.S, b.sum_T)
+        self.ho = torch.zeros(max(self.hob, 1), dtype=torch.uint8, device=b.device)
+        self.args = _dp_args(b, self.outs, self.ws, self.wsb, self.ho, self.hob)
 
     def run(self, stream=None):
         st = ctypes.c_void_p(stream if stream is not None else torch.cuda.current_stream(self.b.device).cuda_stream)
-        if not hasattr(self.lib, "wx_align_dp_ex"):  # an older build under A/B
-            _check(self.lib.wx_align_dp_mode(*self.args[:-2], self.mode, st))
-        else:
-            _check(self.lib.wx_align_dp_ex(*self.args, self.mode, st))
-        return self.seg_start, self.seg_end, self.seg_score, self.t_start, self.status
+        _check(self.lib.wx_align_dp_ex(*self.args, self.mode, st))
+        return self.outs
 
 
 def align_dp_plan(S: int, min_N: int, max_N: int, V: int, mode: int = MODE_AUTO):
@@ -423,15 +387,20 @@ def align_dp_plan(S: int, min_N: int, max_N: int, V: int, mode: int = MODE_AUTO)
     return [x for x in buf.value.decode().split(";") if x]
 
 
-def trellis(b: Batch):
-    """Materialised trellises (CSR): returns (flat tensor, offsets list)."""
+def trellis(b: Batch, out: Optional[torch.Tensor] = None):
+    """Materialised trellises (CSR): returns (flat tensor, offsets list).  `out`: a contiguous
+    float32 tensor on the batch's device with room for every trellis, written instead of a
+    fresh one (a timed loop re-running the launch)."""
     lib = load()
     _validate(b)
     dev = b.device
     offs = [0]
     for T, N in zip(b.Ts, b.Ns):
         offs.append(offs[-1] + (T + 1) * (N + 1))
-    out = torch.empty(max(offs[-1], 1), dtype=torch.float32, device=dev)
+    if out is None:
+        out = torch.empty(max(offs[-1], 1), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.device != dev or not out.is_contiguous() or out.numel() < offs[-1]:
+        raise WXError(f"trellis: out must be a contiguous float32 tensor of >= {offs[-1]} elements on {dev}")
     offs_d = _dev_i64(offs, dev)  # keep referenced until the launch is enqueued
     with torch.cuda.device(dev):
         _check(lib.wx_trellis(_ptr(b.em), _ptr(b.em_off_d), b.V, _ptr(b.tok), _ptr(b.tok_off_d), _ptr(b.blank),
@@ -450,9 +419,9 @@ def backtrack(b: Batch, tr_flat: torch.Tensor, tr_offs):
     plen = torch.empty(max(b.S, 1), dtype=torch.int32, device=dev)
     ts = torch.empty(max(b.S, 1), dtype=torch.int32, device=dev)
     wsb = lib.wx_backtrack_workspace_bytes(b.S, b.sum_T, b.max_N)
-    ws = _ws.get(dev, wsb)
     tr_off_d = _dev_i64(tr_offs, dev)
     with torch.cuda.device(dev):
+        ws = _scratch.get("backtrack", dev, wsb)
         _check(lib.wx_backtrack(_ptr(tr_flat), _ptr(tr_off_d), _ptr(b.em), _ptr(b.em_off_d), b.V,
                                 _ptr(b.tok), _ptr(b.tok_off_d), _ptr(b.blank), b.S, b.max_N, b.sum_T,
                                 _ptr(pt), _ptr(pm), _ptr(pp), _ptr(plen), _ptr(ts), _ptr(ws), wsb, _stream(dev)))
@@ -494,7 +463,6 @@ def binarize(scores_list, sw_geometry, onset: float, offset: float, max_duration
     column); sw_geometry: [(start, step, duration)] per column.  Returns [(starts, ends)]
     as float64 numpy arrays per column.  two_pass picks wx_binarize_ex (bit-word pre-pass +
     event-jumping state machine; the default) or the one-pass scan wx_binarize."""
-    import numpy as np
     lib = load()
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     F = [int(len(s)) for s in scores_list]
@@ -520,7 +488,7 @@ def binarize(scores_list, sw_geometry, onset: float, offset: float, max_duration
     with torch.cuda.device(dev):
         if two_pass:
             wsb = lib.wx_binarize_workspace_bytes(len(F), f_off[-1])
-            ws = _ws_emit.get(f"bin/{dev}/{torch.cuda.current_stream(dev).cuda_stream}", wsb, dev)
+            ws = _scratch.get("binarize", dev, wsb)
             _check(lib.wx_binarize_ex(_ptr(ys), _ptr(f_off_d), len(F), f_off[-1], _ptr(st0), _ptr(stp), _ptr(dur),
                                       float(np.float32(onset)), float(np.float32(offset)), float(max_duration),
                                       float(pad_onset), float(pad_offset), _ptr(rs), _ptr(re), _ptr(r_off_d),
@@ -544,7 +512,6 @@ def binarize(scores_list, sw_geometry, onset: float, offset: float, max_duration
 
 def binarize_plan(onset: float, offset: float, total_frames: int = 1):
     """Kernel names (rocprof form) wx_binarize_ex launches for these thresholds."""
-    import numpy as np
     lib = load(require_device=False)
     buf = ctypes.create_string_buffer(512)
     lib.wx_binarize_plan(float(np.float32(onset)), float(np.float32(offset)), int(total_frames), buf, len(buf))
@@ -703,7 +670,7 @@ def log_mel(wave: torch.Tensor, first, length, pad, filters: torch.Tensor, out: 
     host = [ctypes.c_void_p(ch[i].ctypes.data) for i in range(3)]  # (ch stays referenced through the call)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
-        ws = _ws_emit.get(f"mel/{dev}/{stream.cuda_stream}", wsb, dev)
+        ws = _scratch.get("mel", dev, wsb, stream)
         _check(lib.wx_log_mel(_ptr(wave), int(wave.numel()), host[0], host[1], host[2], _ptr(chunks_d), B,
                               n_mels, _ptr(filters), _ptr(basis), _ptr(out), int(n_frames_max), int(out.stride(1)), _ptr(ws), wsb,
                               ctypes.c_void_p(stream.cuda_stream)))
@@ -786,7 +753,7 @@ def channel_norm(x: torch.Tensor, gamma, beta, eps: float, gelu: bool, out: Opti
     wsb = lib.wx_channel_norm_workspace_bytes(C)
     stream = torch.cuda.current_stream(x.device)
     # one scratch per (device, stream): align() runs forwards on several streams at once
-    ws = _ws_emit.get(f"{x.device}/{stream.cuda_stream}", wsb, x.device)
+    ws = _scratch.get("channel_norm", x.device, wsb, stream)
     with torch.cuda.device(x.device):
         _check(lib.wx_channel_norm(_ptr(x), L, C, _ptr(gamma), _ptr(beta), float(eps), int(bool(gelu)), _ptr(y),
                                    _ptr(ws), ws.numel(), ctypes.c_void_p(stream.cuda_stream)))
@@ -806,7 +773,7 @@ def conv0_channel_norm(x: torch.Tensor, w: torch.Tensor, bias, stride: int, gamm
     if L == 0:
         return y
     stream = torch.cuda.current_stream(x.device)
-    ws = _ws_emit.get(f"{x.device}/{stream.cuda_stream}/c0", lib.wx_conv0_channel_norm_workspace_bytes(L, C), x.device)
+    ws = _scratch.get("conv0", x.device, lib.wx_conv0_channel_norm_workspace_bytes(L, C), stream)
     with torch.cuda.device(x.device):
         _check(lib.wx_conv0_channel_norm(_ptr(x), S, K, int(stride), _ptr(w2), _ptr(bias) if bias is not None else None,
                                          C, _ptr(gamma), _ptr(beta), float(eps), int(bool(gelu)), _ptr(y), _ptr(ws),
@@ -922,15 +889,3 @@ def posconv_packed(h: torch.Tensor, w_packed: torch.Tensor, bias, G: int, K: int
                                      int(K), len(segs.lengths), _ptr(rows_t), _ptr(tiles_t), n_tiles,
                                      int(bool(residual)), _ptr(out), _stream(h.device)))
     return out
-
-
-class _StreamWorkspace(Workspace):
-    def get(self, key, nbytes: int, device=None) -> torch.Tensor:
-        b = self.buf.get(key)
-        if b is None or b.numel() < nbytes:
-            b = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, device=device)
-            self.buf[key] = b
-        return b
-
-
-_ws_emit = _StreamWorkspace()

@@ -3,6 +3,7 @@
 // get_trellis kernel templates live in wx_align_dp.h; their instantiations are compiled in
 // the shards of wx_align_inst.hip.  Every other stage has a file of its own.
 #include "wx_align_dp.h"
+#include "wx_host.h"
 #ifdef WX_PHASE_TIMING  // one TU: the phase-timing device arrays must be a single copy
 #include "wx_align_inst.hip"
 #endif
@@ -243,13 +244,6 @@ using namespace wx;
 
 namespace {
 
-int launch_status() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WX_OK : (int)e;
-}
-
-size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 // Kernels of different (C, W) buckets are independent: a batch that spans several buckets
 // forks them onto a small per-device pool of non-blocking streams and joins back onto the
 // caller's stream with events, so they run concurrently (a latency-bound batch then costs
@@ -287,12 +281,8 @@ ForkPool* fork_pool() {
 template <class F>
 int fork_join(hipStream_t st, int n, F&& launch) {
     if (n <= 0) return WX_OK;
-    if (n == 1) {
-        launch(0, st);
-        return launch_status();
-    }
-    ForkPool* p = fork_pool();
-    if (!p || n > ForkPool::kMax) {  // serial fallback on the caller's stream
+    ForkPool* p = n > 1 && n <= ForkPool::kMax ? fork_pool() : nullptr;
+    if (!p) {  // one launch, or no pool: serially on the caller's stream
         for (int i = 0; i < n; ++i) launch(i, st);
         return launch_status();
     }
@@ -359,14 +349,39 @@ int launch_cells_total(int id, int P) {
     return (id & kSplitFlag) ? bucket_cells_total(id & ~kSplitFlag) * P : bucket_cells_total(id);
 }
 
-// bitmap: per segment (floor(row0/32) + seg) block offsets, 64 * C_stride dwords per block
-size_t bitmap_bytes(int32_t S, int64_t sum_T, int64_t max_N, int* stride_cells) {
+// The hand-off region of split launches, inside the DP workspace or the caller's own:
+// granules per (floor(row0/32) + seg + chunk) block, 3 boundaries x 40, then the arrival words.
+size_t carve_handoff(Carver& c, int32_t S, int64_t sum_T, AlignArgs& a) {
+    a.xg = c.take<uint64_t>((size_t)(sum_T / kChunk + S + 2) * (kMaxParts - 1) * kHaloCells);
+    a.arrive = c.take<uint64_t>((size_t)(S + 1));
+    return c.off;
+}
+
+// The DP workspace: the one statement of its layout (the size query measures it on a null base).
+size_t carve_dp(Carver& c, int32_t S, int64_t sum_T, int64_t max_N, AlignArgs& a) {
     const int nmax = (int)std::max<int64_t>(max_N, 1);  // widest bucket of any launch shape
     int cells = std::max(bucket_cells_total(bucket_id(nmax, 0)), bucket_cells_total(bucket_id(nmax, 1)));
     for (int P = 2; P <= kMaxParts; ++P) cells = std::max(cells, launch_cells_total(split_launch_id(nmax, P), P));
-    if (stride_cells) *stride_cells = cells;
     const int64_t blocks = sum_T / kChunk + S + 1;
-    return align_up((size_t)blocks * (size_t)cells * 4u, 256);
+    // bitmap: per segment (floor(row0/32) + seg) block offsets, 64 * C_stride dwords per block
+    a.bits_stride_cells = cells;
+    a.bits = c.take<unsigned>((size_t)blocks * (size_t)cells);
+    a.q0 = c.take<float>((size_t)(sum_T + 1));
+    a.cmask = c.take<unsigned>((size_t)blocks);
+    a.cn = c.take<float>((size_t)(sum_T + kCnPad * (int64_t)S + 16));  // column N: segment s at (row0 + 4 s) & ~3
+    a.c0acc = c.take<double>((size_t)(blocks + 1));  // checkpointed kernels' column-0 cumsum per chunk (+ seg + q)
+    return carve_handoff(c, S, sum_T, a);  // its own hand-off region: used when the caller passes none
+}
+
+// The backtrack workspace: bitmap, per-token start frames (sum of N <= S * max_N), chunk mask.
+size_t carve_backtrack(Carver& c, int32_t S, int64_t sum_T, int64_t max_N, BacktrackArgs& a) {
+    const int64_t cpl = std::max<int64_t>(1, (max_N + kWave - 1) / kWave);
+    const int64_t blocks = sum_T / kChunk + S + 1;
+    a.bits_stride_cells = (int)(kWave * cpl);
+    a.bits = c.take<unsigned>((size_t)blocks * kWave * (size_t)cpl);
+    a.start = c.take<int32_t>((size_t)(S * max_N + 1));
+    a.cmask = c.take<unsigned>((size_t)blocks);
+    return c.off;
 }
 
 }  // namespace
@@ -400,22 +415,10 @@ int align_mode(int32_t S, int32_t mode) {
     return S <= 256 ? WX_MODE_LATENCY : WX_MODE_THROUGHPUT;
 }
 
-size_t cmask_bytes(int32_t S, int64_t sum_T) { return align_up((size_t)(sum_T / kChunk + S + 1) * 4u, 256); }
-
-// column N history: segment s at (row0 + 4 s) & ~3 (16-byte aligned groups of 8 rows)
-size_t cn_bytes(int32_t S, int64_t sum_T) { return align_up((size_t)(sum_T + kCnPad * (int64_t)S + 16) * 4u, 256); }
-
-// split hand-off granules: per (floor(row0/32) + seg + chunk) block, 3 boundaries x 40
-size_t xg_bytes(int32_t S, int64_t sum_T) {
-    return align_up((size_t)(sum_T / kChunk + S + 2) * (kMaxParts - 1) * kHaloCells * 8u, 256);
-}
-size_t arrive_bytes(int32_t S) { return align_up((size_t)(S + 1) * 8u, 256); }
-// checkpointed kernels' column-0 cumsum per chunk: (floor(row0/32) + seg + q) doubles
-size_t c0acc_bytes(int32_t S, int64_t sum_T) { return align_up((size_t)(sum_T / kChunk + S + 2) * 8u, 256); }
-
 size_t wx_align_dp_workspace_bytes(int32_t S, int64_t sum_T, int64_t max_N) {
-    return bitmap_bytes(S, sum_T, max_N, nullptr) + align_up((size_t)(sum_T + 1) * 4u, 256) + cmask_bytes(S, sum_T) +
-           cn_bytes(S, sum_T) + c0acc_bytes(S, sum_T) + xg_bytes(S, sum_T) + arrive_bytes(S);
+    Carver c{nullptr};
+    AlignArgs a;
+    return carve_dp(c, S, sum_T, max_N, a);
 }
 
 // CUs of the current device (cached per device).
@@ -482,7 +485,11 @@ static int split_flags() {
     return (on("WX_SPLIT_FENCED") ? kArgFenced : 0) | (on("WX_SPLIT_XCD_SPREAD") ? kArgXcdSpread : 0);
 }
 
-size_t wx_align_dp_handoff_bytes(int32_t S, int64_t sum_T) { return xg_bytes(S, sum_T) + arrive_bytes(S); }
+size_t wx_align_dp_handoff_bytes(int32_t S, int64_t sum_T) {
+    Carver c{nullptr};
+    AlignArgs a;
+    return carve_handoff(c, S, sum_T, a);
+}
 
 int wx_align_dp(const float* em, const int64_t* em_off, int32_t V, const int32_t* tok, const int64_t* tok_off,
                 const int32_t* blank_id, int32_t S, int64_t min_N, int64_t max_N, int64_t sum_T, int32_t* seg_start,
@@ -517,20 +524,12 @@ int wx_align_dp_ex(const float* em, const int64_t* em_off, int32_t V, const int3
     if (V > 32) return WX_E_INVALID;  // development build: only the V <= 32 kernels exist
 #endif
     if (max_N > WX_MAX_TOKENS) return WX_E_TOO_LONG;
-    if (workspace_bytes < wx_align_dp_workspace_bytes(S, sum_T, max_N)) return WX_E_WORKSPACE;
-    if (handoff && handoff_bytes < wx_align_dp_handoff_bytes(S, sum_T)) return WX_E_WORKSPACE;
     AlignArgs a;
+    Carver ws{workspace}, ho{handoff};  // (the caller's hand-off region takes the place of the workspace's)
+    if (workspace_bytes < carve_dp(ws, S, sum_T, max_N, a)) return WX_E_WORKSPACE;
+    if (handoff && handoff_bytes < carve_handoff(ho, S, sum_T, a)) return WX_E_WORKSPACE;
     a.em = em; a.em_off = em_off; a.V = V; a.tok = tok; a.tok_off = tok_off; a.blank_id = blank_id; a.S = S;
     a.seg_start = seg_start; a.seg_end = seg_end; a.seg_score = seg_score; a.t_start = t_start; a.status = status;
-    const size_t bm = bitmap_bytes(S, sum_T, max_N, &a.bits_stride_cells);
-    a.bits = reinterpret_cast<unsigned*>(workspace);
-    a.q0 = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + bm);
-    a.cmask = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) + bm +
-                                          align_up((size_t)(sum_T + 1) * 4u, 256));
-    a.cn = reinterpret_cast<float*>(reinterpret_cast<char*>(a.cmask) + cmask_bytes(S, sum_T));
-    a.c0acc = reinterpret_cast<double*>(reinterpret_cast<char*>(a.cn) + cn_bytes(S, sum_T));
-    a.xg = reinterpret_cast<uint64_t*>(handoff ? handoff : reinterpret_cast<char*>(a.c0acc) + c0acc_bytes(S, sum_T));
-    a.arrive = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(a.xg) + xg_bytes(S, sum_T));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     a.mode = align_mode(S, mode);
     a.parts = split_parts(S, a.mode, mode);
@@ -626,11 +625,9 @@ int wx_trellis(const float* em, const int64_t* em_off, int32_t V, const int32_t*
 }
 
 size_t wx_backtrack_workspace_bytes(int32_t S, int64_t sum_T, int64_t max_N) {
-    const int64_t cpl = std::max<int64_t>(1, (max_N + kWave - 1) / kWave);
-    const int64_t blocks = sum_T / kChunk + S + 1;
-    // bitmap + per-token start frames (sum of N <= S * max_N)
-    return align_up((size_t)blocks * kWave * (size_t)cpl * 4u, 256) + align_up((size_t)(S * max_N + 1) * 4u, 256) +
-           cmask_bytes(S, sum_T);
+    Carver c{nullptr};
+    BacktrackArgs a;
+    return carve_backtrack(c, S, sum_T, max_N, a);
 }
 
 int wx_backtrack(const float* trellis, const int64_t* tr_off, const float* em, const int64_t* em_off, int32_t V,
@@ -643,19 +640,12 @@ int wx_backtrack(const float* trellis, const int64_t* tr_off, const float* em, c
         !path_len || !t_start || !workspace)
         return WX_E_INVALID;
     if (V < 1) return WX_E_VOCAB;
-    if (workspace_bytes < wx_backtrack_workspace_bytes(S, sum_T, max_N)) return WX_E_WORKSPACE;
     BacktrackArgs a;
+    Carver ws{workspace};
+    if (workspace_bytes < carve_backtrack(ws, S, sum_T, max_N, a)) return WX_E_WORKSPACE;
     a.tr = trellis; a.tr_off = tr_off; a.em = em; a.em_off = em_off; a.V = V; a.tok = tok; a.tok_off = tok_off;
     a.blank_id = blank_id; a.path_tok = path_tok; a.path_time = path_time; a.path_prob = path_prob;
     a.path_len = path_len; a.t_start = t_start;
-    const int64_t cpl = std::max<int64_t>(1, (max_N + kWave - 1) / kWave);
-    a.bits_stride_cells = (int)(kWave * cpl);
-    const int64_t blocks = sum_T / kChunk + S + 1;
-    const size_t bm = align_up((size_t)blocks * kWave * (size_t)cpl * 4u, 256);
-    a.bits = reinterpret_cast<unsigned*>(workspace);
-    a.start = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + bm);
-    a.cmask = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) + bm +
-                                          align_up((size_t)(S * max_N + 1) * 4u, 256));
     hipLaunchKernelGGL(backtrack_kernel, dim3(S), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
     return launch_status();
 }

@@ -7,7 +7,7 @@
 #include <stdio.h>
 #include <string.h>
 
-#include "../../include/wx_align.h"
+#include "wx_host.h"  // (and through it include/wx_align.h)
 #include "wx_wave.h"
 
 namespace wx {
@@ -818,13 +818,6 @@ using namespace wx;
 
 namespace {
 
-int launch_status() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WX_OK : (int)e;
-}
-
-size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 // The argument checks wx_binarize and wx_binarize_ex share, and the kernels' arguments (the
 // pointers may be null when n_files == 0: the caller returns before any launch).
 int binarize_args(const float* scores, const int64_t* f_off, int32_t n_files, const double* sw_start,
@@ -839,6 +832,19 @@ int binarize_args(const float* scores, const int64_t* f_off, int32_t n_files, co
     a.onset = onset; a.offset = offset; a.maxd = max_duration; a.pad_on = pad_onset; a.pad_off = pad_offset;
     a.rs = reg_start; a.re = reg_end; a.reg_off = reg_off; a.reg_count = reg_count;
     return WX_OK;
+}
+
+// The two-pass workspace, stated once: pass 1's words, then the scan kernel's region lists (F + 1 per file).
+size_t carve_binarize(Carver& c, int32_t n_files, int64_t total_frames, BinScanArgs& sa) {
+    const size_t nw = (size_t)bin_words(total_frames, n_files);
+    const size_t nl = (size_t)total_frames + (size_t)n_files;
+    sa.w.on = c.take<unsigned long long>(nw);
+    sa.w.off = c.take<unsigned long long>(nw);
+    sa.w.mv = c.take<float>(nw);
+    sa.w.mi = c.take<int32_t>(nw);
+    sa.ra = c.take<int32_t>(nl);
+    sa.rd = c.take<int32_t>(nl);
+    return c.off;
 }
 
 // offset <= onset: no frame both sets and resets the state, so the parallel scan is exact
@@ -862,9 +868,9 @@ int wx_binarize(const float* scores, const int64_t* f_off, int32_t n_files, cons
 
 size_t wx_binarize_workspace_bytes(int32_t n_files, int64_t total_frames) {
     if (n_files < 0 || total_frames < 0) return 0;
-    const size_t nw = (size_t)bin_words(total_frames, n_files);
-    const size_t nl = (size_t)total_frames + (size_t)n_files;  // region lists, F + 1 per file
-    return 2 * align_up(nw * 8u, 256) + 2 * align_up(nw * 4u, 256) + 2 * align_up(nl * 4u, 256);
+    Carver c{nullptr};
+    BinScanArgs sa;
+    return carve_binarize(c, n_files, total_frames, sa);
 }
 
 int wx_binarize_ex(const float* scores, const int64_t* f_off, int32_t n_files, int64_t total_frames,
@@ -878,35 +884,21 @@ int wx_binarize_ex(const float* scores, const int64_t* f_off, int32_t n_files, i
                                  pad_onset, pad_offset, reg_start, reg_end, reg_off, reg_count, a);
     if (rc != WX_OK || n_files == 0) return rc;
     if (!workspace) return WX_E_INVALID;
-    if (workspace_bytes < wx_binarize_workspace_bytes(n_files, total_frames)) return WX_E_WORKSPACE;
+    BinScanArgs sa;
+    sa.a = a;
+    Carver ws{workspace};
+    if (workspace_bytes < carve_binarize(ws, n_files, total_frames, sa)) return WX_E_WORKSPACE;
     const int64_t nw = bin_words(total_frames, n_files);
-    char* p = reinterpret_cast<char*>(workspace);
-    BinWords w;
-    w.on = reinterpret_cast<unsigned long long*>(p);
-    p += align_up((size_t)nw * 8u, 256);
-    w.off = reinterpret_cast<unsigned long long*>(p);
-    p += align_up((size_t)nw * 8u, 256);
-    w.mv = reinterpret_cast<float*>(p);
-    p += align_up((size_t)nw * 4u, 256);
-    w.mi = reinterpret_cast<int32_t*>(p);
-    p += align_up((size_t)nw * 4u, 256);
-    const size_t nl = (size_t)total_frames + (size_t)n_files;
-    int32_t* ra = reinterpret_cast<int32_t*>(p);
-    p += align_up(nl * 4u, 256);
-    int32_t* rd = reinterpret_cast<int32_t*>(p);
     BinWordArgs wa;
     wa.y = scores; wa.f_off = f_off; wa.n_files = n_files; wa.n_words = nw; wa.onset = onset; wa.offset = offset;
-    wa.w = w;
+    wa.w = sa.w;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (total_frames > 0)  // (its tile loads read frame 0 for words past a file's end)
         hipLaunchKernelGGL(binarize_words_kernel, dim3((unsigned)((nw + kWave - 1) / kWave)), dim3(kWave), 0, s, wa);
-    if (binarize_uses_scan(onset, offset)) {
-        BinScanArgs sa;
-        sa.a = a; sa.w = w; sa.ra = ra; sa.rd = rd;
+    if (binarize_uses_scan(onset, offset))
         hipLaunchKernelGGL(binarize_scan_kernel, dim3(n_files), dim3(kBinWG), 0, s, sa);
-    } else {
-        hipLaunchKernelGGL(binarize_fsm_kernel, dim3(n_files), dim3(kWave), 0, s, a, w);
-    }
+    else
+        hipLaunchKernelGGL(binarize_fsm_kernel, dim3(n_files), dim3(kWave), 0, s, a, sa.w);
     return launch_status();
 }
 

@@ -16,7 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/wx_align.h"
+#include "wx_host.h"  // (and through it include/wx_align.h)
 
 namespace wxd {
 
@@ -149,6 +149,5 @@ extern "C" int wx_assign_speakers(const double* turn_start, const double* turn_e
     hipLaunchKernelGGL(assign_speakers_kernel, dim3((unsigned)waves), dim3(kWave), 0,
                        reinterpret_cast<hipStream_t>(stream), turn_start, turn_end, turn_off, grp_off, q_start, q_end,
                        q_off, speaker, best_sum, a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WX_OK : (int)e;
+    return wx::launch_status();
 }

@@ -12,7 +12,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "../../include/wx_align.h"
+#include "wx_host.h"  // (and through it include/wx_align.h)
 
 namespace wxe {
 
@@ -799,8 +799,7 @@ extern "C" int wx_channel_norm(const float* x, int64_t L, int32_t C, const float
     const int64_t n4 = L * (C / 4);
     hipLaunchKernelGGL(chan_apply_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, x, n4, C / 4, ab, C,
                        gelu, y);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WX_OK : (int)e;
+    return wx::launch_status();
 }
 
 extern "C" size_t wx_conv0_channel_norm_workspace_bytes(int64_t L, int32_t C) {
@@ -822,19 +821,16 @@ extern "C" int wx_conv0_channel_norm(const float* x, int64_t S, int32_t K, int32
     const int64_t nblk = (L + rows_per_blk - 1) / rows_per_blk;
     if (nblk > 65535) return WX_E_INVALID;  // (grid y; ~4.2 h of 16 kHz audio at stride 5)
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    double* part = reinterpret_cast<double*>(workspace);
+    float* ab = reinterpret_cast<float*>(part + (size_t)nblk * 2 * C);
     if (rl) {
-        double* part = reinterpret_cast<double*>(workspace);
-        float* ab = reinterpret_cast<float*>(part + (size_t)nblk * 2 * C);
         const dim3 grid((C + 63) / 64, (unsigned)nblk);
         hipLaunchKernelGGL((conv0_stats_rl_kernel<10, 5>), grid, dim3(256), 0, st, x, S, L, w, bias, C, part);
         hipLaunchKernelGGL(conv0_finish_kernel, dim3((C + kCols - 1) / kCols), dim3(kCols * kRows), 0, st, part,
                            (int)nblk, L, C, gamma, beta, eps, ab);
         hipLaunchKernelGGL((conv0_apply_rl_kernel<10, 5>), grid, dim3(256), 0, st, x, S, L, w, bias, C, ab, gelu, y);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? WX_OK : (int)e;
+        return wx::launch_status();
     }
-    double* part = reinterpret_cast<double*>(workspace);
-    float* ab = reinterpret_cast<float*>(part + (size_t)nblk * 2 * C);
     const dim3 grid((C + kCols - 1) / kCols, (unsigned)nblk), blk(kCols * kRows);
 #define WX_C0(KK)                                                                                              \
     case KK:                                                                                                   \
@@ -849,8 +845,7 @@ extern "C" int wx_conv0_channel_norm(const float* x, int64_t S, int32_t K, int32
         default: return WX_E_INVALID;
     }
 #undef WX_C0
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WX_OK : (int)e;
+    return wx::launch_status();
 }
 
 extern "C" int wx_attention_f32(const float* q, const float* k, const float* v, float* o, int32_t B, int32_t H,
@@ -891,8 +886,7 @@ extern "C" int wx_attention_f32(const float* q, const float* k, const float* v, 
     const dim3 grid((unsigned)((int64_t)(T + 31) / 32 * B * H));
     hipLaunchKernelGGL((attn_f32_kernel<kAttnSplit, false>), grid, dim3(64 * kAttnSplit), 0,
                        reinterpret_cast<hipStream_t>(stream), a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WX_OK : (int)e;
+    return wx::launch_status();
 }
 
 
@@ -941,8 +935,7 @@ extern "C" int wx_attention_f32_packed(const float* q, const float* k, const flo
         case 4: hipLaunchKernelGGL((attn_f32_kernel<4, true>), dim3((unsigned)n_units), dim3(256), 0, s, a); break;
         default: return WX_E_INVALID;
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WX_OK : (int)e;
+    return wx::launch_status();
 }
 
 extern "C" int wx_add_layernorm(const float* a, const float* b, int64_t rows, int32_t D, int64_t a_stride,
@@ -964,8 +957,7 @@ extern "C" int wx_add_layernorm(const float* a, const float* b, int64_t rows, in
         case 768: hipLaunchKernelGGL(add_ln_kernel<3>, grid, dim3(256), 0, st, a, b, gamma, beta, eps, rows, a_stride, b_stride, (int64_t)D, y, sum_out); break;
         default: hipLaunchKernelGGL(add_ln_kernel<4>, grid, dim3(256), 0, st, a, b, gamma, beta, eps, rows, a_stride, b_stride, (int64_t)D, y, sum_out); break;
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WX_OK : (int)e;
+    return wx::launch_status();
 }
 
 extern "C" int wx_posconv_packed(const float* h, int32_t D, const float* w_packed, const float* bias, int32_t G,
@@ -994,6 +986,5 @@ extern "C" int wx_posconv_packed(const float* h, int32_t D, const float* w_packe
         case 64: hipLaunchKernelGGL(posconv_kernel<64>, grid, dim3(256), 0, s, a); break;
         default: return WX_E_INVALID;
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WX_OK : (int)e;
+    return wx::launch_status();
 }

@@ -34,7 +34,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-#include "../../include/wx_align.h"
+#include "wx_host.h"  // (and through it include/wx_align.h)
 
 namespace wxm {
 
@@ -338,6 +338,5 @@ extern "C" int wx_log_mel(const float* wave, int64_t n_wave, const int64_t* chun
     if (e != hipSuccess) return (int)e;
     const dim3 fgrid((unsigned)((max_frames + 255) / 256), (unsigned)n_mels, (unsigned)B);
     hipLaunchKernelGGL(log_mel_finish_kernel, fgrid, dim3(256), 0, st, a);
-    e = hipGetLastError();
-    return e == hipSuccess ? WX_OK : (int)e;
+    return wx::launch_status();
 }

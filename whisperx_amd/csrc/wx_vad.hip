@@ -19,7 +19,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "../../include/wx_align.h"
+#include "wx_host.h"  // (and through it include/wx_align.h)
 
 namespace wxv {
 
@@ -515,8 +515,7 @@ extern "C" int wx_sincnet_stage_ex(const float* x, int64_t B, int64_t L, int32_t
     a.in_scale = in_scale;
     a.in_shift = in_shift;
     hipLaunchKernelGGL(sinc_stage_kernel, dim3((unsigned)B), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WX_OK : (int)e;
+    return wx::launch_status();
 }
 
 extern "C" int wx_sincnet_stage(const float* x, int64_t B, int64_t L, int32_t C, int64_t x_window_stride,
@@ -537,8 +536,7 @@ extern "C" int wx_lstm_bidir_layer(const float* xp, const float* whh, float* y, 
     const dim3 grid((unsigned)((B + kLR - 1) / kLR), 2);
     hipLaunchKernelGGL(lstm_layer_kernel, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), xp, whh, y,
                        (int)B, (int)T);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WX_OK : (int)e;
+    return wx::launch_status();
 }
 
 extern "C" int wx_sinc_filterbank(const float* x, int64_t n, int32_t stride, const float* w_padded, int32_t C,
@@ -554,8 +552,7 @@ extern "C" int wx_sinc_filterbank(const float* x, int64_t n, int32_t stride, con
         hipLaunchKernelGGL((sinc_fb_kernel<5, 260>), grid, dim3(64 * 5), 0, s, x, n, (int)stride, w_padded, y, F);
     else
         return WX_E_INVALID;
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WX_OK : (int)e;
+    return wx::launch_status();
 }
 
 extern "C" int wx_conv1d_taps_tm(const float* x, int64_t B, int64_t L, int32_t Cin, const float* w_packed,
@@ -575,8 +572,7 @@ extern "C" int wx_conv1d_taps_tm(const float* x, int64_t B, int64_t L, int32_t C
                            (int)Lout);
     else
         return WX_E_INVALID;
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WX_OK : (int)e;
+    return wx::launch_status();
 }
 
 extern "C" int wx_vad_aggregate(const float* scores, const int64_t* start_frame, int32_t n_chunks,
@@ -591,6 +587,5 @@ extern "C" int wx_vad_aggregate(const float* scores, const int64_t* start_frame,
     a.n_classes = n_classes; a.n_frames = n_frames; a.missing = missing; a.out = out;
     const unsigned blocks = (unsigned)((n_frames + 255) / 256);
     hipLaunchKernelGGL(vad_aggregate_kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? WX_OK : (int)e;
+    return wx::launch_status();
 }
