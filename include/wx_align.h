@@ -27,6 +27,9 @@
  *                        transcript_result, fill_nearest), every segment and word of a corpus
  *   wx_log_mel        <- whisperx/audio.py:140-159  log_mel_spectrogram(audio, n_mels, padding),
  *                        every VAD chunk of a file (asr.py:141-149 preprocess) in one launch
+ *   wx_whisper_stem   <- whisperx/asr.py:77-86  WhisperModel.encode (the audio encoder's two
+ *                        convolutions, GELUs and positional table, fused; the layers above it
+ *                        run on wx_attention_f32 and wx_add_layernorm)
  *
  * Conventions
  *   - All data pointers are DEVICE pointers (allocated by the caller; the library never
@@ -280,7 +283,8 @@ int wx_posconv_packed(const float* h, int32_t D, const float* w_packed, const fl
 
 /* wav2vec2 encoder layer's residual add + LayerNorm (alignment.py:226-233, the emission
  * forward: `layer_norm(residual + x)` twice per layer): for each of `rows` rows of D floats
- * (D in {256, 512, 768, 1024}; row strides a_stride / b_stride elements, multiples of 4; all
+ * (D in {256, 384, 512, 768, 1024, 1280}: wav2vec2's widths and Whisper's, whose pre-norm layers
+ * take sum_out as the residual stream; row strides a_stride / b_stride elements, multiples of 4; all
  * pointers 16-byte aligned), s = a + b, y = (s - mean(s)) / sqrt(var(s) + eps) * gamma + beta
  * (biased variance, fp32, two passes over the row in registers).  y is [rows][D] contiguous;
  * sum_out (may be NULL) receives s in the same layout.  Equal to torch's add + LayerNorm to
@@ -410,6 +414,34 @@ int wx_log_mel(const float* wave, int64_t n_wave, const int64_t* chunk_first, co
                const int64_t* chunk_pad, const int64_t* chunks_dev, int32_t B, int32_t n_mels,
                const float* filters, const float* basis, float* out, int64_t n_frames_max,
                int64_t row_stride, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The stem of Whisper's audio encoder (asr.py:77-86: WhisperModel.encode hands the features to
+ * the ASR engine; the arithmetic is transformers' WhisperEncoder.forward), batched over B chunks:
+ *     a1[b][t][:] = gelu(b1 + sum_{j<3} W1[:, :, j] . x[b][:, t - 1 + j])          t in [0, Tin)
+ *     out[b][u][:] = gelu(b2 + sum_{j<3} W2[:, :, j] . a1[b][2u - 1 + j][:]) + pos[u][:]   u in [0, Tin / 2)
+ *   with x = 0 outside [0, Tin) and a1 = 0 at row -1 of every chunk (Conv1d padding 1; the
+ *   padding is the chunk's own, never a neighbouring chunk's row), gelu the exact erf form, fp32.
+ *   x: chunk b, mel row m at x + b x_batch_stride + m x_row_stride (elements; x_row_stride >= Tin,
+ *   4-byte alignment suffices): wx_log_mel's output, or a slice of it with fewer frames, is read
+ *   in place.  n_mels: 80 or 128.  Tin even, >= 2.  D: a multiple of 64, at most 1280.
+ *   w1_packed / w2_packed: conv1.weight [D][n_mels][3] / conv2.weight [D][D][3] packed as
+ *   v_mfma_f32_16x16x4_f32 A fragments, [D / 16 tiles][3 taps][Cin / 16 groups][64 lanes][4] fp32
+ *   (16-byte aligned): entry [ot][j][g][lane][i] = W[16 ot + lane % 16][16 g + 4 (lane / 16) + i][j].
+ *   b1, b2 [D]; pos [Tin / 2][D] (embed_positions); out [B][Tin / 2][D] time-major contiguous; all
+ *   16-byte aligned.  workspace: wx_whisper_stem_workspace_bytes(B, Tin, D) bytes (16-byte
+ *   aligned); after the call it holds a1 [B][Tin][D] time-major, the one intermediate.
+ * Two launches on `stream`, one per convolution, each an implicit GEMM over a time-major LDS
+ * window (no patch buffer, no channel-major intermediate; bias, GELU and the positional row in
+ * the epilogue).  Tiles are per chunk: chunk b's values are bit-identical whatever B is.  f32
+ * MFMA: equal to torch's conv1d to fp32 tolerance, not bit-identical.
+ * B < 0, Tin odd or < 2 (or above 2^24), another n_mels, D not a multiple of 64 or above 1280:
+ * WX_E_INVALID; then B == 0: WX_OK; B > 65535, x_row_stride < Tin, a negative batch stride, a null
+ * or misaligned pointer: WX_E_INVALID; a short workspace: WX_E_WORKSPACE; all before anything is
+ * enqueued. */
+size_t wx_whisper_stem_workspace_bytes(int32_t B, int32_t Tin, int32_t D);
+int wx_whisper_stem(const float* x, int64_t x_batch_stride, int64_t x_row_stride, int32_t B, int32_t n_mels,
+                    int32_t Tin, const float* w1_packed, const float* b1, const float* w2_packed, const float* b2,
+                    const float* pos, int32_t D, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

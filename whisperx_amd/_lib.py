@@ -23,7 +23,7 @@ LIB_PATH = os.environ.get("WX_LIB_PATH") or os.path.join(_HERE, "libwxalign.so")
 SRC_PATH = os.path.join(_HERE, "csrc", "wx_align.hip")
 SRC_PATHS = [SRC_PATH, os.path.join(_HERE, "csrc", "wx_binarize.hip"), os.path.join(_HERE, "csrc", "wx_emission.hip"),
              os.path.join(_HERE, "csrc", "wx_vad.hip"), os.path.join(_HERE, "csrc", "wx_diarize.hip"),
-             os.path.join(_HERE, "csrc", "wx_mel.hip")]
+             os.path.join(_HERE, "csrc", "wx_mel.hip"), os.path.join(_HERE, "csrc", "wx_whisper.hip")]
 INST_PATH = os.path.join(_HERE, "csrc", "wx_align_inst.hip")
 HDR_PATHS = [os.path.join(_HERE, "csrc", "wx_align_dp.h"), os.path.join(_HERE, "csrc", "wx_wave.h"),
              os.path.join(_HERE, "csrc", "wx_host.h"), INST_PATH]
@@ -103,6 +103,8 @@ SIGNATURES = {
                                           _vp, _vp, _vp]),
     "wx_log_mel_workspace_bytes": (_sz, [_i32]),
     "wx_log_mel": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _vp, _sz, _vp]),
+    "wx_whisper_stem_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "wx_whisper_stem": (ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
 }
 
 
@@ -674,6 +676,50 @@ def log_mel(wave: torch.Tensor, first, length, pad, filters: torch.Tensor, out: 
         _check(lib.wx_log_mel(_ptr(wave), int(wave.numel()), host[0], host[1], host[2], _ptr(chunks_d), B,
                               n_mels, _ptr(filters), _ptr(basis), _ptr(out), int(n_frames_max), int(out.stride(1)), _ptr(ws), wsb,
                               ctypes.c_void_p(stream.cuda_stream)))
+    return out
+
+
+def pack_conv3_weight(w: torch.Tensor) -> torch.Tensor:
+    """A Conv1d(Cin, D, 3) weight [D, Cin, 3] packed as wx_whisper_stem reads it (include/wx_align.h):
+    [D / 16][3][Cin / 16][64 lanes][4], entry [ot][j][g][lane][i] = w[16 ot + lane % 16][16 g + 4 (lane / 16) + i][j]."""
+    D, Cin, K = (int(v) for v in w.shape)
+    if K != 3 or D % 16 or Cin % 16:
+        raise WXError(f"pack_conv3_weight: weight {tuple(w.shape)} is not [16 a, 16 b, 3]")
+    # [ot, o16, g, q, i, j] -> [ot, j, g, q, o16, i]: lane = 16 q + o16
+    return (w.detach().to(torch.float32).reshape(D // 16, 16, Cin // 16, 4, 4, 3).permute(0, 5, 2, 3, 1, 4)
+            .contiguous().reshape(D // 16, 3, Cin // 16, 64, 4))
+
+
+def whisper_stem(x: torch.Tensor, w1_packed: torch.Tensor, b1: torch.Tensor, w2_packed: torch.Tensor,
+                 b2: torch.Tensor, pos: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """wx_whisper_stem: x [B, n_mels, Tin] fp32 device features (frames contiguous, any batch / row
+    stride: a slice of log_mel's output is read in place) -> [B, Tin / 2, D] time-major rows,
+    gelu(conv2(gelu(conv1(x)))) + pos, on the current stream.  w*_packed: pack_conv3_weight of the
+    two conv weights; pos [Tin / 2, D].  `out`: a contiguous [B, Tin / 2, D] tensor (or slice) to
+    write into instead of a fresh one."""
+    lib = load()
+    if x.dim() != 3 or x.dtype != torch.float32 or not x.is_cuda or (x.shape[2] > 1 and x.stride(2) != 1):
+        raise WXError("whisper_stem: x must be a float32 [B, n_mels, Tin] device tensor with contiguous frames")
+    B, M, Tin = (int(v) for v in x.shape)
+    D = int(b1.numel())
+    dev = x.device
+    for t in (w1_packed, b1, w2_packed, b2, pos):
+        if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
+            raise WXError("whisper_stem: weights must be contiguous float32 tensors on the features' device")
+    if w1_packed.numel() != 3 * M * D or w2_packed.numel() != 3 * D * D or b2.numel() != D \
+            or tuple(pos.shape) != (Tin // 2, D):
+        raise WXError(f"whisper_stem: weights do not fit n_mels {M}, D {D}, {Tin} frames")
+    if out is None:
+        out = torch.empty((B, Tin // 2, D), dtype=torch.float32, device=dev)
+    if tuple(out.shape) != (B, Tin // 2, D) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+        raise WXError("whisper_stem: out must be a contiguous float32 [B, Tin / 2, D] tensor on the features' device")
+    wsb = lib.wx_whisper_stem_workspace_bytes(B, Tin, D)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        ws = _scratch.get("whisper_stem", dev, wsb, stream)
+        _check(lib.wx_whisper_stem(_ptr(x), int(x.stride(0)) if B > 1 else M * int(x.stride(1)), int(x.stride(1)),
+                                   B, M, Tin, _ptr(w1_packed), _ptr(b1), _ptr(w2_packed), _ptr(b2), _ptr(pos), D,
+                                   _ptr(out), _ptr(ws), ws.numel(), ctypes.c_void_p(stream.cuda_stream)))
     return out
 
 

@@ -600,7 +600,9 @@ __global__ __launch_bounds__(64 * SPLIT) __attribute__((amdgpu_waves_per_eu(2)))
 // float4 per lane), mean and biased variance in fp32 from the registers (two passes, not
 // torch's Welford: equal to fp32 tolerance), y = (s - mean) * rstd * gamma + beta.  Optionally
 // also writes the sum s (the pre-norm residual stream of the stable-layer-norm layers).
-template <int NV>  // float4 per lane: D = 256 NV
+// D4 < 64 NV (Whisper-tiny's D = 384: 96 float4): the lanes past the row's end hold zeros and
+// skip their loads and stores; the full-width instantiations compile as before.
+template <int NV, int D4 = 64 * NV>  // NV float4 per lane, D4 per row: D = 4 D4
 __global__ __launch_bounds__(256) void add_ln_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
                                                       float eps, int64_t rows, int64_t sa, int64_t sb, int64_t sy,
@@ -608,13 +610,19 @@ __global__ __launch_bounds__(256) void add_ln_kernel(const float* __restrict__ a
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const int l = threadIdx.x & 63;
-    constexpr int D = 256 * NV;
+    constexpr int D = 4 * D4;
+    constexpr bool kFull = D4 == 64 * NV;
+    static_assert(D4 <= 64 * NV && D4 > 64 * (NV - 1), "NV float4 per lane cover the row");
     const float4* pa = reinterpret_cast<const float4*>(a + row * sa);
     const float4* pb = reinterpret_cast<const float4*>(b + row * sb);
     float4 v[NV];
     float acc = 0.0f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
+        if (!kFull && 64 * i + l >= D4) {
+            v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            continue;
+        }
         const float4 x = pa[64 * i + l], z = pb[64 * i + l];
         v[i] = make_float4(x.x + z.x, x.y + z.y, x.z + z.z, x.w + z.w);
         acc += (v[i].x + v[i].y) + (v[i].z + v[i].w);
@@ -625,6 +633,7 @@ __global__ __launch_bounds__(256) void add_ln_kernel(const float* __restrict__ a
     float q = 0.0f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
+        if (!kFull && 64 * i + l >= D4) continue;
         const float dx = v[i].x - mean, dy = v[i].y - mean, dz = v[i].z - mean, dw = v[i].w - mean;
         q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
     }
@@ -637,6 +646,7 @@ __global__ __launch_bounds__(256) void add_ln_kernel(const float* __restrict__ a
     const float4* pt = reinterpret_cast<const float4*>(beta);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
+        if (!kFull && 64 * i + l >= D4) continue;
         const float4 g = pg[64 * i + l], t = pt[64 * i + l];
         py[64 * i + l] = make_float4((v[i].x - mean) * rstd * g.x + t.x, (v[i].y - mean) * rstd * g.y + t.y,
                                      (v[i].z - mean) * rstd * g.z + t.z, (v[i].w - mean) * rstd * g.w + t.w);
@@ -942,7 +952,7 @@ extern "C" int wx_add_layernorm(const float* a, const float* b, int64_t rows, in
                                 int64_t b_stride, const float* gamma, const float* beta, float eps, float* y,
                                 float* sum_out, void* stream) {
     using namespace wxe;
-    if (rows < 0 || (D != 768 && D != 1024 && D != 512 && D != 256)) return WX_E_INVALID;
+    if (rows < 0 || (D != 768 && D != 1024 && D != 512 && D != 256 && D != 384 && D != 1280)) return WX_E_INVALID;
     if (rows == 0) return WX_OK;  // (an empty tensor may have no storage)
     if (!a || !b || !gamma || !beta || !y) return WX_E_INVALID;
     if (a_stride < D || b_stride < D || (a_stride & 3) || (b_stride & 3)) return WX_E_INVALID;
@@ -955,6 +965,8 @@ extern "C" int wx_add_layernorm(const float* a, const float* b, int64_t rows, in
         case 256: hipLaunchKernelGGL(add_ln_kernel<1>, grid, dim3(256), 0, st, a, b, gamma, beta, eps, rows, a_stride, b_stride, (int64_t)D, y, sum_out); break;
         case 512: hipLaunchKernelGGL(add_ln_kernel<2>, grid, dim3(256), 0, st, a, b, gamma, beta, eps, rows, a_stride, b_stride, (int64_t)D, y, sum_out); break;
         case 768: hipLaunchKernelGGL(add_ln_kernel<3>, grid, dim3(256), 0, st, a, b, gamma, beta, eps, rows, a_stride, b_stride, (int64_t)D, y, sum_out); break;
+        case 384: hipLaunchKernelGGL((add_ln_kernel<2, 96>), grid, dim3(256), 0, st, a, b, gamma, beta, eps, rows, a_stride, b_stride, (int64_t)D, y, sum_out); break;
+        case 1280: hipLaunchKernelGGL(add_ln_kernel<5>, grid, dim3(256), 0, st, a, b, gamma, beta, eps, rows, a_stride, b_stride, (int64_t)D, y, sum_out); break;
         default: hipLaunchKernelGGL(add_ln_kernel<4>, grid, dim3(256), 0, st, a, b, gamma, beta, eps, rows, a_stride, b_stride, (int64_t)D, y, sum_out); break;
     }
     return wx::launch_status();

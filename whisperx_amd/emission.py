@@ -370,7 +370,7 @@ def _fuse_qkv(model: torch.nn.Module) -> None:
             m.forward = types.MethodType(f, m)
 
 
-_ADDLN_WIDTHS = (256, 512, 768, 1024)
+_ADDLN_WIDTHS = (256, 384, 512, 768, 1024, 1280)  # wx_add_layernorm's (384 and 1280: Whisper tiny / large)
 
 
 def _addln_ok(layer, x: torch.Tensor, norms) -> bool:
