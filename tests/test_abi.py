@@ -3,6 +3,8 @@ no compute calls; argument validation paths return before any launch)."""
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 
@@ -186,3 +188,25 @@ def test_binarize_plan_kernel_selection(lib):
     assert _lib.binarize_plan(0.5, 0.5, 1000) == [words, scan]
     assert _lib.binarize_plan(0.4, 0.6, 1000) == [words, fsm]
     assert _lib.binarize_plan(0.5, 0.55, 0) == [fsm]
+
+
+CSRC = os.path.join(ROOT, "whisperx_amd", "csrc")
+
+
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))
+# the DP headers also with the phase-timing macros' bodies (wx_dp_timing.h)
+HEADER_BUILDS = [(h, "") for h in HEADERS] + [(h, "-DWX_PHASE_TIMING") for h in HEADERS if "_dp" in h]
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc is not installed")
+@pytest.mark.parametrize("header,flag", HEADER_BUILDS)
+def test_header_compiles_on_its_own(header, flag, tmp_path):
+    """Every csrc header includes what it uses: a translation unit of that one #include passes
+    hipcc's syntax check for gfx950 with the build's flags."""
+    from whisperx_amd import _lib
+
+    tu = tmp_path / "tu.hip"
+    tu.write_text(f'#include "{os.path.join(CSRC, header)}"\n')
+    res = subprocess.run(["hipcc", *_lib.BASE_FLAGS, *flag.split(), f"-I{_lib.INCLUDE_DIR}", "-x", "hip",
+                          "-fsyntax-only", str(tu)], capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr

@@ -249,7 +249,7 @@ def test_align_dp_speculative_walk_trimmed_segments():
 
 def _capacity(C, W):
     """Tokens a (C cells/lane, W waves) bucket holds: waves >= 1 give ceil(32/C) lanes to the
-    chunk halo (wx_align_dp.h, Geometry)."""
+    chunk halo (wx_dp_config.h, Geometry)."""
     return C * (64 + (W - 1) * (64 - ((32 + C - 1) // C if W > 1 else 0)))
 
 

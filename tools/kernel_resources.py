@@ -4,18 +4,13 @@ import os
 import re
 import subprocess
 import sys
-import tempfile
 
-LLVM = "/opt/rocm/lib/llvm/bin"
+from codeobj import code_object, llvm
 
 
 def notes(so):
-    with tempfile.TemporaryDirectory() as d:
-        fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "k.co")
-        subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", so], check=True)
-        subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}",
-                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True)
-        txt = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], capture_output=True, text=True).stdout
+    with code_object(so) as co:
+        txt = llvm("llvm-readelf", "--notes", co)
     # the metadata keys of a kernel are sorted: those before ".name" (group_segment_fixed_size)
     # belong to the kernel whose name follows
     out, cur, pending = [], {}, {}

@@ -9,6 +9,7 @@ the library sees raw device pointers, sizes and the current HIP stream.
 from __future__ import annotations
 
 import ctypes
+import glob
 import os
 import subprocess
 import threading
@@ -25,8 +26,7 @@ SRC_PATHS = [SRC_PATH, os.path.join(_HERE, "csrc", "wx_binarize.hip"), os.path.j
              os.path.join(_HERE, "csrc", "wx_vad.hip"), os.path.join(_HERE, "csrc", "wx_diarize.hip"),
              os.path.join(_HERE, "csrc", "wx_mel.hip"), os.path.join(_HERE, "csrc", "wx_whisper.hip")]
 INST_PATH = os.path.join(_HERE, "csrc", "wx_align_inst.hip")
-HDR_PATHS = [os.path.join(_HERE, "csrc", "wx_align_dp.h"), os.path.join(_HERE, "csrc", "wx_wave.h"),
-             os.path.join(_HERE, "csrc", "wx_host.h"), INST_PATH]
+HDR_PATHS = sorted(glob.glob(os.path.join(_HERE, "csrc", "*.h"))) + [INST_PATH]  # (a new header: a rebuild)
 INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 
 MAX_VOCAB = 16384

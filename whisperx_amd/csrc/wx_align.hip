@@ -1,12 +1,27 @@
 // wx_align.hip — the alignment's host C ABI (include/wx_align.h) and its non-template kernels
 // (materialised-trellis backtrack, merge_repeats, column-0 cumsum).  The fused DP and
-// get_trellis kernel templates live in wx_align_dp.h; their instantiations are compiled in
-// the shards of wx_align_inst.hip.  Every other stage has a file of its own.
-#include "wx_align_dp.h"
+// get_trellis kernel templates live in wx_align_dp.h and its wx_dp_*.h (this file includes only
+// what plans a launch and what backtrack_kernel shares with them); their instantiations are
+// compiled in the shards of wx_align_inst.hip.  Every other stage has a file of its own.
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <mutex>
+
+#include "wx_dp_config.h"
+#include "wx_dp_prims.h"
+#include "wx_dp_tail.h"
+#include "wx_dp_walk.h"
 #include "wx_host.h"
 #ifdef WX_PHASE_TIMING  // one TU: the phase-timing device arrays must be a single copy
 #include "wx_align_inst.hip"
 #endif
+
+#define WX_VERSION "0.1.0"
 
 namespace wx {
 

@@ -1,5 +1,5 @@
 // wx_align_inst.hip — explicit instantiations of the fused-DP, split and get_trellis kernel
-// templates (wx_align_dp.h), one launcher per (bucket, row width).  Compiled once per shard
+// templates (wx_align_dp.h and its wx_dp_*.h), one launcher per (bucket, row width).  Compiled once per shard
 // (-DWX_SHARD=0..7) so that the ~90 kernel instantiations build in parallel; without
 // WX_SHARD every instantiation is compiled (a single-TU build, e.g. WX_PHASE_TIMING).
 #include "wx_align_dp.h"
@@ -31,7 +31,7 @@ void launch_trellis(dim3 grid, hipStream_t s, const TrellisArgs& a) {
 #define WX_SPLIT(C, W) WX_EACH_VS(WX_I_SPLIT, C, W)
 #define WX_TR(C, W) WX_EACH_VS(WX_I_TR, C, W)
 
-// Every bucket of WX_BUCKETS / WX_SPLIT_BUCKETS (wx_align_dp.h) must appear once below; a
+// Every bucket of WX_BUCKETS / WX_SPLIT_BUCKETS (wx_dp_config.h) must appear once below; a
 // missing one fails at link time (undefined launcher).
 #if !defined(WX_SHARD) || WX_SHARD == 0
 WX_ALIGN(1, 1, 0) WX_ALIGN(2, 1, 0) WX_ALIGN(4, 1, 0)

@@ -1,4 +1,4 @@
-// wx_wave.h — the wave64 helpers shared by the alignment DP (wx_align_dp.h) and Binarize
+// wx_wave.h — the wave64 helpers shared by the alignment DP (wx_dp_*.h) and Binarize
 // (wx_binarize.hip): lane index, and wave-uniform (SGPR) copies of per-lane values.
 #ifndef WX_WAVE_H
 #define WX_WAVE_H
