@@ -30,6 +30,9 @@
  *   wx_whisper_stem   <- whisperx/asr.py:77-86  WhisperModel.encode (the audio encoder's two
  *                        convolutions, GELUs and positional table, fused; the layers above it
  *                        run on wx_attention_f32 and wx_add_layernorm)
+ *   wx_decode_attention_f32 <- whisperx/asr.py:53-62, 245-257  generate_segment_batched and
+ *                        detect_language (the text decoder's self- and cross-attention of one
+ *                        decode step: one query row per sequence and head)
  *
  * Conventions
  *   - All data pointers are DEVICE pointers (allocated by the caller; the library never
@@ -442,6 +445,36 @@ size_t wx_whisper_stem_workspace_bytes(int32_t B, int32_t Tin, int32_t D);
 int wx_whisper_stem(const float* x, int64_t x_batch_stride, int64_t x_row_stride, int32_t B, int32_t n_mels,
                     int32_t Tin, const float* w1_packed, const float* b1, const float* w2_packed, const float* b2,
                     const float* pos, int32_t D, float* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Attention of one decode step of Whisper's text decoder (asr.py:53-62: generate_segment_batched
+ * hands the encoder output to the ASR engine; the arithmetic is transformers' WhisperDecoder.forward
+ * with its key / value cache): one query row per (batch, head) against L key / value rows,
+ *     o[b][h][:] = sum_{j<L} softmax_j(scale * q[b][h][:] . k[b][h][j][:]) v[b][h][j][:]
+ *   fp32, no mask, head dim D == 64 only.
+ *   q: row (b, h) at q + b q_strides[0] + h q_strides[1]; k / v: row (b, h, j) at
+ *   k + b k_strides[0] + h k_strides[1] + j k_strides[2], v likewise (the stride arrays are HOST
+ *   arrays, in elements; the head dim is contiguous; every stride a multiple of 4 and every data
+ *   pointer 16-byte aligned, so that rows are).  K and V are
+ *   read in place: the self-attention cache [B][H][Lcap][64] with L = the tokens so far, or the two
+ *   halves of the cross-attention GEMM output [B][P][2 H 64] (row stride 2 H 64, head stride 64).
+ *   Rows j >= L are never read.  o: [B][H][64] contiguous; nothing else is written.
+ *   workspace: wx_decode_attention_workspace_bytes(B, H, L) bytes (16-byte aligned); after the call
+ *   it holds the chunks' partial results (m, l) and acc[64].
+ * The keys are cut into chunks of WX_DECODE_ATTENTION_CHUNK rows, a constant; one workgroup per
+ * (chunk, head, batch) computes the chunk's softmax maximum m, sum l and weighted value sum, and a
+ * second launch merges the chunks of every (batch, head) in chunk order (no launch for one chunk,
+ * which the first kernel finishes itself).  No atomics, no hand-shake between workgroups.  Neither
+ * the chunking nor any summation order depends on B or H: row (b, h) is bit-identical whatever the
+ * batch is.  Equal to torch's scaled_dot_product_attention to fp32 tolerance, not bit-identical.
+ * B < 0, H < 1, L < 1, D != 64: WX_E_INVALID; then B == 0: WX_OK; a null or misaligned pointer, a
+ * stride that is no multiple of 4, B or H above 65535 (grid dimensions): WX_E_INVALID; a short
+ * workspace: WX_E_WORKSPACE; all before anything is enqueued. */
+#define WX_DECODE_ATTENTION_CHUNK 128
+size_t wx_decode_attention_workspace_bytes(int32_t B, int32_t H, int32_t L);
+int wx_decode_attention_f32(const float* q, const float* k, const float* v, float* o, int32_t B, int32_t H,
+                            int32_t L, int32_t D, const int64_t* q_strides, const int64_t* k_strides,
+                            const int64_t* v_strides, float scale, void* workspace, size_t workspace_bytes,
+                            void* stream);
 
 #ifdef __cplusplus
 }

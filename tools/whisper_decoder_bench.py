@@ -1,0 +1,219 @@
+#!/usr/bin/env python3
+"""Times of Whisper's text decoder, one position per step (no threshold: a record).
+
+Random weights in two geometries (--geometries, comma separated), vocabulary 51865, 448 target
+positions, 1500 encoder positions:
+  base      D 512, 6 layers, 8 heads
+  large-v2  D 1280, 32 layers, 20 heads
+
+(a) attention: wx_decode_attention_f32 (whisperx_amd._lib.decode_attention_f32) against
+    F.scaled_dot_product_attention on the same tensors, at L = 1500 (the cross-attention layout: the
+    halves of a [B, 1500, 2D] tensor) and L = 224 (the cache layout [B, H, 448, 64]), B in {1, 16}.
+    Each arm is the median of --repeat repetitions (with min and max, the spread a difference has to
+    exceed) of --steps launches between device events.  The launches of a repetition walk a ring of
+    key / value buffers of --ring-bytes in all, so that a launch does not find its rows in the cache
+    the launch before left.  Reported with the time: the key / value bytes the shapes say are read
+    (2 B H L 64 x 4), and that over the time as bytes/s and as a share of the HBM peak.
+(b) decoder: one `step` of 16 rows at position 35 (the state's position is put back before every
+    call), and `generate` of 64 tokens for 16 chunks from a 3-token prompt, against transformers'
+    fp32 WhisperDecoder with its key / value cache in a greedy loop of the same length on the same
+    device (its per-step figure is that loop's time over its 64 steps; it takes the prompt in one
+    forward, ours in three steps).  Both loops check for completion, and so synchronise, every step.
+
+Prints one JSON line; --out writes it to a file (profiles/whisper_decoder_<host>.json).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+HBM_PEAK_BYTES_PER_S = 8.0e12  # MI355X HBM3E, spec
+GEOMETRIES = {"base": {"D": 512, "layers": 6}, "large-v2": {"D": 1280, "layers": 32}}
+V, T, P = 51865, 448, 1500
+PROMPT = [50258, 50259, 50359]
+N_TOKENS, CHUNKS, STEP_POS = 64, 16, 35
+
+
+def summary(times):
+    return {"median_s": statistics.median(times), "min_s": min(times), "max_s": max(times), "repeat": len(times)}
+
+
+def timed(fn, repeat, warmup, sync):
+    for _ in range(warmup):
+        fn()
+    sync()
+    out = []
+    for _ in range(repeat):
+        t0 = time.perf_counter()
+        fn()
+        sync()
+        out.append(time.perf_counter() - t0)
+    return summary(out)
+
+
+def event_timed(fn, repeat, warmup, steps, torch):
+    """fn(i): launch number i of a repetition."""
+    for i in range(warmup):
+        fn(i)
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(repeat):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(steps):
+            fn(i)
+        e1.record()
+        torch.cuda.synchronize()
+        times.append(e0.elapsed_time(e1) / 1e3 / steps)
+    s = summary(times)
+    s["steps"] = steps
+    return s
+
+
+def beats(a, b):
+    return {"speedup_median": b["median_s"] / a["median_s"], "not_slower_median": bool(a["median_s"] <= b["median_s"]),
+            "beats_beyond_spread": bool(a["max_s"] < b["min_s"])}
+
+
+def attention_rows(D, args, torch, F, _lib, dev):
+    H = D // 64
+    rows = []
+    for L, layout in ((1500, "cross [B, L, 2D] halves"), (224, "cache [B, H, 448, 64]")):
+        for B in (1, 16):
+            nbytes = 2 * B * H * L * 64 * 4
+            ring = max(2, min(32, -(-args.ring_bytes // nbytes)))
+            q = torch.randn((B, H, 64), device=dev)
+            kv = []
+            for _ in range(ring):
+                if L == 1500:
+                    t = torch.randn((B, L, 2 * D), device=dev)
+                    kv.append(tuple(t[:, :, j * D:(j + 1) * D].view(B, L, H, 64).transpose(1, 2) for j in range(2)))
+                else:
+                    kv.append((torch.randn((B, H, T, 64), device=dev), torch.randn((B, H, T, 64), device=dev)))
+            out = torch.empty((B, H, 64), device=dev)
+
+            def ours(i):
+                k, v = kv[i % ring]
+                return _lib.decode_attention_f32(q, k, v, 0.125, L=L, out=out)
+
+            def sdpa(i):
+                k, v = kv[i % ring]
+                return F.scaled_dot_product_attention(q.unsqueeze(2), k[:, :, :L], v[:, :, :L], scale=0.125)
+
+            with torch.inference_mode():
+                diff = float((ours(0) - sdpa(0).squeeze(2)).abs().max())
+                r = {"L": L, "B": B, "H": H, "layout": layout, "kv_bytes": nbytes, "ring_buffers": ring,
+                     "max_abs_diff_ours_vs_sdpa": diff,
+                     "ours": event_timed(ours, args.repeat, args.warmup, args.steps, torch),
+                     "sdpa": event_timed(sdpa, args.repeat, args.warmup, args.steps, torch)}
+            for arm in ("ours", "sdpa"):
+                r[arm]["kv_bytes_per_s"] = nbytes / r[arm]["median_s"]
+                r[arm]["share_of_hbm_peak"] = r[arm]["kv_bytes_per_s"] / HBM_PEAK_BYTES_PER_S
+            r["ours_vs_sdpa"] = beats(r["ours"], r["sdpa"])
+            rows.append(r)
+            del kv
+            torch.cuda.empty_cache()
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--geometries", default="base,large-v2")
+    ap.add_argument("--repeat", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=50, help="launches per repetition of the attention and step arms")
+    ap.add_argument("--ring-bytes", type=int, default=1 << 30, help="key / value bytes the attention arms cycle through")
+    ap.add_argument("--seed", type=int, default=12)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    import torch.nn.functional as F
+    from transformers import WhisperConfig, WhisperForConditionalGeneration
+
+    from whisperx_amd import WhisperDecoder, _lib
+
+    if not torch.cuda.is_available():
+        raise SystemExit("whisper_decoder_bench: needs a HIP device")
+    dev = torch.device("cuda", 0)
+    sync = torch.cuda.synchronize
+    result = {"tool": "tools/whisper_decoder_bench.py", "device": torch.cuda.get_device_name(0),
+              "lib": os.path.basename(_lib.LIB_PATH), "dtype": "float32", "decode_chunk": _lib.DECODE_CHUNK,
+              "peaks": {"hbm_bytes_per_s": HBM_PEAK_BYTES_PER_S}, "geometries": {}}
+    eot = V - 1  # suppressed: both greedy loops run their full length
+    for name in args.geometries.split(","):
+        g = GEOMETRIES[name]
+        D = g["D"]
+        torch.manual_seed(args.seed)
+        r = {"shape": {**g, "heads": D // 64, "vocab": V, "max_target_positions": T, "encoder_positions": P}}
+        r["attention"] = attention_rows(D, args, torch, F, _lib, dev)
+        cfg = WhisperConfig(d_model=D, encoder_layers=1, encoder_attention_heads=1, encoder_ffn_dim=64, num_mel_bins=80,
+                            max_source_positions=P, decoder_layers=g["layers"], decoder_attention_heads=D // 64,
+                            decoder_ffn_dim=4 * D, vocab_size=V, max_target_positions=T, pad_token_id=0, bos_token_id=1,
+                            eos_token_id=2, decoder_start_token_id=1)
+        hf = WhisperForConditionalGeneration(cfg).eval().model.decoder.to(dev)
+        for p in hf.parameters():
+            p.requires_grad_(False)
+        r["shape"]["attn_implementation"] = cfg._attn_implementation
+        ours = WhisperDecoder(hf, device=dev)
+        enc = torch.randn((CHUNKS, P, D), device=dev)
+        prompt = torch.tensor([PROMPT] * CHUNKS, device=dev)
+
+        def hf_generate():
+            with torch.inference_mode():
+                o = hf(input_ids=prompt, encoder_hidden_states=enc, use_cache=True)
+                steps = []
+                for _ in range(N_TOKENS):
+                    lg = F.linear(o.last_hidden_state[:, -1], hf.embed_tokens.weight)
+                    lg[:, eot] = float("-inf")
+                    nxt = lg.argmax(-1)
+                    steps.append(nxt)
+                    if bool((nxt == eot).all()):
+                        break
+                    if len(steps) < N_TOKENS:
+                        o = hf(input_ids=nxt[:, None], encoder_hidden_states=enc, past_key_values=o.past_key_values,
+                               use_cache=True)
+                return torch.stack(steps, 1)
+
+        def ours_generate():
+            return ours.generate(enc, PROMPT, eot, max_length=len(PROMPT) + N_TOKENS, suppress_tokens=[eot])
+
+        got, want = torch.tensor(ours_generate()), hf_generate().cpu()
+        r["generated_tokens"] = int(got.shape[1])
+        r["greedy_tokens_equal_hf"] = float((got == want).float().mean())  # (fp32 against fp32 on flat random logits)
+        r["generate"] = timed(ours_generate, args.repeat, args.warmup, sync)
+        r["hf_generate"] = timed(hf_generate, args.repeat, args.warmup, sync)
+        r["generate_vs_hf"] = beats(r["generate"], r["hf_generate"])
+        r["hf_step_from_generate"] = {k: v / N_TOKENS for k, v in r["hf_generate"].items() if k.endswith("_s")}
+        st = ours.start(enc)
+        tok = torch.full((CHUNKS,), 7, dtype=torch.int64, device=dev)
+        for _ in range(STEP_POS):
+            ours.step(st, tok)
+
+        def step(i):
+            st.pos = STEP_POS
+            return ours._step(st, tok)
+
+        with torch.inference_mode():
+            r["step"] = event_timed(step, args.repeat, args.warmup, args.steps, torch)
+        r["step"]["rows"], r["step"]["position"] = CHUNKS, STEP_POS
+        result["geometries"][name] = r
+        del hf, ours, enc, st
+        torch.cuda.empty_cache()
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(json.dumps(result, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -24,7 +24,8 @@ LIB_PATH = os.environ.get("WX_LIB_PATH") or os.path.join(_HERE, "libwxalign.so")
 SRC_PATH = os.path.join(_HERE, "csrc", "wx_align.hip")
 SRC_PATHS = [SRC_PATH, os.path.join(_HERE, "csrc", "wx_binarize.hip"), os.path.join(_HERE, "csrc", "wx_emission.hip"),
              os.path.join(_HERE, "csrc", "wx_vad.hip"), os.path.join(_HERE, "csrc", "wx_diarize.hip"),
-             os.path.join(_HERE, "csrc", "wx_mel.hip"), os.path.join(_HERE, "csrc", "wx_whisper.hip")]
+             os.path.join(_HERE, "csrc", "wx_mel.hip"), os.path.join(_HERE, "csrc", "wx_whisper.hip"),
+             os.path.join(_HERE, "csrc", "wx_decode.hip")]
 INST_PATH = os.path.join(_HERE, "csrc", "wx_align_inst.hip")
 HDR_PATHS = sorted(glob.glob(os.path.join(_HERE, "csrc", "*.h"))) + [INST_PATH]  # (a new header: a rebuild)
 INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
@@ -105,6 +106,8 @@ SIGNATURES = {
     "wx_log_mel": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _vp, _sz, _vp]),
     "wx_whisper_stem_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "wx_whisper_stem": (ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
+    "wx_decode_attention_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "wx_decode_attention_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _vp, _sz, _vp]),
 }
 
 
@@ -720,6 +723,45 @@ def whisper_stem(x: torch.Tensor, w1_packed: torch.Tensor, b1: torch.Tensor, w2_
         _check(lib.wx_whisper_stem(_ptr(x), int(x.stride(0)) if B > 1 else M * int(x.stride(1)), int(x.stride(1)),
                                    B, M, Tin, _ptr(w1_packed), _ptr(b1), _ptr(w2_packed), _ptr(b2), _ptr(pos), D,
                                    _ptr(out), _ptr(ws), ws.numel(), ctypes.c_void_p(stream.cuda_stream)))
+    return out
+
+
+DECODE_CHUNK = 128  # WX_DECODE_ATTENTION_CHUNK (include/wx_align.h): keys per workgroup of wx_decode_attention_f32
+
+
+def decode_attention_f32(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, L: Optional[int] = None,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """wx_decode_attention_f32: one query row per (batch, head), q [B, H, 64], against rows 0 .. L - 1
+    of k / v [B, H, Lcap, 64] (L defaults to Lcap): fp32 device views of any batch / head / row
+    stride with a contiguous head dim and 16-byte aligned rows, read in place (the self-attention
+    cache, or the halves of the cross-attention [B, P, 2 H 64] GEMM output).  Returns [B, H, 64]
+    contiguous (`out` when given) on the current stream."""
+    lib = load()
+    if q.dim() != 3 or k.dim() != 4 or v.dim() != 4:
+        raise WXError(f"decode_attention_f32: q {tuple(q.shape)} / k {tuple(k.shape)} / v {tuple(v.shape)} are not "
+                      "[B, H, 64] / [B, H, Lcap, 64] / [B, H, Lcap, 64]")
+    B, H, D = (int(x) for x in q.shape)
+    Lcap = int(k.shape[2])
+    L = Lcap if L is None else int(L)
+    if tuple(k.shape) != (B, H, Lcap, D) or tuple(v.shape) != (B, H, Lcap, D) or not 1 <= L <= Lcap:
+        raise WXError(f"decode_attention_f32: k {tuple(k.shape)} / v {tuple(v.shape)} do not hold {L} rows for q "
+                      f"{tuple(q.shape)}")
+    dev = q.device
+    for t in (q, k, v):
+        if t.dtype != torch.float32 or not t.is_cuda or t.device != dev or t.stride(-1) != 1:
+            raise WXError("decode_attention_f32: q, k and v must be float32 tensors on one HIP device with a contiguous "
+                          "head dim")
+    if out is None:
+        out = torch.empty((B, H, D), dtype=torch.float32, device=dev)
+    if tuple(out.shape) != (B, H, D) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+        raise WXError("decode_attention_f32: out must be a contiguous float32 [B, H, 64] tensor on the queries' device")
+    st = [(ctypes.c_int64 * n)(*(int(x) for x in t.stride()[:n])) for t, n in ((q, 2), (k, 3), (v, 3))]
+    wsb = lib.wx_decode_attention_workspace_bytes(B, H, L)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        ws = _scratch.get("decode_attention", dev, wsb, stream)
+        _check(lib.wx_decode_attention_f32(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, H, L, D, st[0], st[1], st[2],
+                                           float(scale), _ptr(ws), ws.numel(), ctypes.c_void_p(stream.cuda_stream)))
     return out
 
 
