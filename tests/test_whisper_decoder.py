@@ -9,7 +9,8 @@ import pytest
 import torch
 
 from whisper_decoder_helpers import (GEOMETRIES, PROMPT, case, check_detect_language, check_forced_logits, check_greedy,
-                                     check_stopping, check_suppression, openai_names)
+                                     check_stopping, check_suppression)
+from whisper_helpers import openai_names
 
 SMALL = GEOMETRIES[0]
 
@@ -45,7 +46,7 @@ def test_every_weight_form_gives_the_same_tensors():
     sd = {k: v.clone() for k, v in model.model.decoder.state_dict().items()}
     for prefix in ("", "decoder.", "model.decoder."):
         assert _same(_host({prefix + k: v for k, v in sd.items()}), want), prefix
-    assert _same(_host(openai_names(sd)), want)
+    assert _same(_host(openai_names(sd, "decoder")), want)
     # a dict of a whole model: the encoder's tensors are ignored, the tied proj_out.weight accepted
     whole = dict(model.state_dict())
     assert "proj_out.weight" in whole and any(k.startswith("model.encoder.") for k in whole)

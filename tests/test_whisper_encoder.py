@@ -36,7 +36,7 @@ def test_every_weight_form_gives_the_same_output():
     sd = {k: v.clone() for k, v in enc.state_dict().items()}
     for prefix in ("", "encoder.", "model.encoder."):
         assert torch.equal(_host({prefix + k: v for k, v in sd.items()}).encode(x), want), prefix
-    assert torch.equal(_host(openai_names(sd)).encode(x), want)
+    assert torch.equal(_host(openai_names(sd, "encoder")).encode(x), want)
     # a dict of a whole model: the decoder's tensors are ignored
     with_dec = {"model.encoder." + k: v for k, v in sd.items()}
     with_dec["model.decoder.layers.0.fc1.weight"] = torch.zeros(4, 4)

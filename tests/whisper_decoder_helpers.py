@@ -2,9 +2,9 @@
 the oracle.
 
 No weights are downloaded: the model is built from a tiny WhisperConfig and its decoder's weights
-are drawn by whisper_helpers.make_encoder's recipe (unit-variance fan-in scaling, q and k
-projections 3x that, biases ~0.1, LayerNorm gains 1 +- 0.1, positional table 0.5 randn) with one
-change: embed_tokens.weight is randn / sqrt(D).  At unit variance the tied output projection makes
+are drawn by whisper_helpers.draw_weights (unit-variance fan-in scaling, q and k projections 3x
+that, biases ~0.1, LayerNorm gains 1 +- 0.1, positional table 0.5 randn) with
+embed_tokens.weight randn / sqrt(D).  At unit variance the tied output projection makes
 the model echo its last input token for ever (logits ~200, top-2 margin ~50) and any attention bug
 would pass; with 1 / sqrt(D) the greedy sequences vary and the logits are O(4).
 
@@ -18,6 +18,8 @@ import copy
 import functools
 
 import torch
+
+from whisper_helpers import draw_weights
 
 # (D, layers, P, V, max_target_positions, B): the geometries of the decoder tests
 GEOMETRIES = [(384, 2, 50, 96, 40, 3), (1280, 1, 33, 96, 24, 2), (512, 1, 130, 96, 24, 2)]
@@ -37,24 +39,8 @@ def make_model(D: int, layers: int, P: int, V: int, T: int, seed: int = 0):
                         decoder_ffn_dim=4 * D, vocab_size=V, max_target_positions=T, pad_token_id=0, bos_token_id=1,
                         eos_token_id=2, decoder_start_token_id=1, dropout=0.0, attention_dropout=0.0,
                         activation_dropout=0.0, decoder_layerdrop=0.0, scale_embedding=False)
-    model = WhisperForConditionalGeneration(cfg).eval()
-    g = torch.Generator().manual_seed(seed)
-    with torch.no_grad():
-        for name, p in model.model.decoder.named_parameters():
-            if name.endswith("bias"):
-                p.copy_(0.1 * torch.randn(p.shape, generator=g))
-            elif "layer_norm" in name:  # LayerNorm gains around 1
-                p.copy_(1.0 + 0.1 * torch.randn(p.shape, generator=g))
-            elif name == "embed_positions.weight":
-                p.copy_(0.5 * torch.randn(p.shape, generator=g))
-            elif name == "embed_tokens.weight":
-                p.copy_(torch.randn(p.shape, generator=g) / D ** 0.5)
-            else:
-                fan_in = p[0].numel()
-                scale = 3.0 if (".q_proj." in name or ".k_proj." in name) else 1.0
-                p.copy_(scale * torch.randn(p.shape, generator=g) / fan_in ** 0.5)
-    for p in model.parameters():
-        p.requires_grad_(False)
+    model = WhisperForConditionalGeneration(cfg).eval().requires_grad_(False)
+    draw_weights(model.model.decoder, seed, embed_tokens_div=D ** 0.5)
     assert model.proj_out.weight.data_ptr() == model.model.decoder.embed_tokens.weight.data_ptr()  # tied
     return model
 
@@ -115,30 +101,6 @@ class Case:
 @functools.lru_cache(maxsize=None)
 def case(D, layers, P, V, T, B) -> Case:
     return Case(D, layers, P, V, T, B)
-
-
-def openai_names(sd: dict) -> dict:
-    """An HF-named decoder state dict (no prefix) under OpenAI's names (decoder.blocks.N...)."""
-    ren = {"self_attn.q_proj": "attn.query", "self_attn.k_proj": "attn.key", "self_attn.v_proj": "attn.value",
-           "self_attn.out_proj": "attn.out", "self_attn_layer_norm": "attn_ln", "encoder_attn.q_proj": "cross_attn.query",
-           "encoder_attn.k_proj": "cross_attn.key", "encoder_attn.v_proj": "cross_attn.value",
-           "encoder_attn.out_proj": "cross_attn.out", "encoder_attn_layer_norm": "cross_attn_ln", "fc1": "mlp.0",
-           "fc2": "mlp.2", "final_layer_norm": "mlp_ln"}
-    out = {}
-    for k, v in sd.items():
-        if k == "embed_positions.weight":
-            out["decoder.positional_embedding"] = v
-        elif k == "embed_tokens.weight":
-            out["decoder.token_embedding.weight"] = v
-        elif k.startswith("layers."):
-            _, n, rest = k.split(".", 2)
-            mod, leaf = rest.rsplit(".", 1)
-            out[f"decoder.blocks.{n}.{ren[mod]}.{leaf}"] = v
-        elif k.startswith("layer_norm."):
-            out["decoder.ln." + k.split(".", 1)[1]] = v
-        else:
-            raise KeyError(k)
-    return out
 
 
 def attention_inputs(B: int, H: int, L: int, seed: int = 0):

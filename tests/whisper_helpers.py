@@ -1,4 +1,5 @@
-"""Shared by the Whisper encoder tests: a random transformers WhisperEncoder as the oracle.
+"""Shared by the Whisper tests: a random transformers WhisperEncoder as the encoder's oracle, and the
+weight recipe and OpenAI renaming that the decoder's helpers (whisper_decoder_helpers) use too.
 
 No weights are downloaded: the module is built from a tiny WhisperConfig with
 max_source_positions = P and its weights are drawn here.  transformers' default 0.02 init makes
@@ -27,23 +28,29 @@ def make_encoder(D: int, layers: int, P: int, n_mels: int = 80, seed: int = 0):
                         decoder_ffn_dim=64, vocab_size=64, pad_token_id=0, bos_token_id=1, eos_token_id=2,
                         decoder_start_token_id=1, dropout=0.0, attention_dropout=0.0, activation_dropout=0.0,
                         encoder_layerdrop=0.0)
-    enc = WhisperEncoder(cfg).eval()
+    return draw_weights(WhisperEncoder(cfg).eval(), seed)
+
+
+def draw_weights(module, seed: int, embed_tokens_div: float = 1.0):
+    """The recipe of this file's docstring on every parameter of `module`, in named_parameters()
+    order from one generator, then frozen; embed_tokens.weight (the decoder's, tied to its output
+    projection) is randn / embed_tokens_div.  Returns `module`."""
     g = torch.Generator().manual_seed(seed)
     with torch.no_grad():
-        for name, p in enc.named_parameters():
+        for name, p in module.named_parameters():
             if name.endswith("bias"):
                 p.copy_(0.1 * torch.randn(p.shape, generator=g))
             elif "layer_norm" in name:  # LayerNorm gains around 1
                 p.copy_(1.0 + 0.1 * torch.randn(p.shape, generator=g))
             elif name == "embed_positions.weight":
                 p.copy_(0.5 * torch.randn(p.shape, generator=g))
+            elif name == "embed_tokens.weight":
+                p.copy_(torch.randn(p.shape, generator=g) / embed_tokens_div)
             else:
                 fan_in = p[0].numel()
                 scale = 3.0 if (".q_proj." in name or ".k_proj." in name) else 1.0
                 p.copy_(scale * torch.randn(p.shape, generator=g) / fan_in ** 0.5)
-    for p in enc.parameters():
-        p.requires_grad_(False)
-    return enc
+    return module.requires_grad_(False)
 
 
 def make_features(B: int, n_mels: int, frames: int, seed: int = 1) -> torch.Tensor:
@@ -64,23 +71,29 @@ def case(D: int, layers: int, P: int, B: int, n_mels: int = 80):
     return enc, x, y64, ref_err
 
 
-def openai_names(sd: dict) -> dict:
-    """An HF-named encoder state dict (no prefix) under OpenAI's names (encoder.blocks.N...)."""
-    ren = {"self_attn.q_proj": "attn.query", "self_attn.k_proj": "attn.key", "self_attn.v_proj": "attn.value",
-           "self_attn.out_proj": "attn.out", "self_attn_layer_norm": "attn_ln", "fc1": "mlp.0", "fc2": "mlp.2",
-           "final_layer_norm": "mlp_ln"}
-    out = {}
+# transformers' names inside `layers.N.` -> OpenAI's inside `blocks.N.`; the top-level names per part
+_OPENAI_BLOCK = {"self_attn.q_proj": "attn.query", "self_attn.k_proj": "attn.key", "self_attn.v_proj": "attn.value",
+                 "self_attn.out_proj": "attn.out", "self_attn_layer_norm": "attn_ln", "encoder_attn.q_proj": "cross_attn.query",
+                 "encoder_attn.k_proj": "cross_attn.key", "encoder_attn.v_proj": "cross_attn.value",
+                 "encoder_attn.out_proj": "cross_attn.out", "encoder_attn_layer_norm": "cross_attn_ln", "fc1": "mlp.0",
+                 "fc2": "mlp.2", "final_layer_norm": "mlp_ln"}
+_OPENAI_TOP = {"encoder": {"embed_positions.weight": "positional_embedding", "layer_norm": "ln_post", "conv1": "conv1",
+                           "conv2": "conv2"},
+               "decoder": {"embed_positions.weight": "positional_embedding", "layer_norm": "ln",
+                           "embed_tokens": "token_embedding"}}
+
+
+def openai_names(sd: dict, part: str) -> dict:
+    """An HF-named state dict of `part` ("encoder" / "decoder", no prefix) under OpenAI's names
+    (`<part>.blocks.N...`).  A key that OpenAI's model does not have is a KeyError."""
+    top, out = _OPENAI_TOP[part], {}
     for k, v in sd.items():
-        if k == "embed_positions.weight":
-            out["encoder.positional_embedding"] = v
-        elif k.startswith("layers."):
-            _, n, rest = k.split(".", 2)
-            mod, leaf = rest.rsplit(".", 1)
-            out[f"encoder.blocks.{n}.{ren[mod]}.{leaf}"] = v
-        elif k.startswith("layer_norm."):
-            out["encoder.ln_post." + k.split(".", 1)[1]] = v
+        mod, leaf = k.rsplit(".", 1)
+        if k.startswith("layers."):
+            _, n, mod = mod.split(".", 2)
+            out[f"{part}.blocks.{n}.{_OPENAI_BLOCK[mod]}.{leaf}"] = v
         else:
-            out["encoder." + k] = v
+            out[f"{part}." + (top[k] if k in top else f"{top[mod]}.{leaf}")] = v
     return out
 
 

@@ -29,37 +29,17 @@ import ctypes
 import json
 import os
 import platform
-import statistics
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+from benchlib import event_timed, timed  # noqa: E402
 
 HBM_PEAK_BPS = 8.0e12        # MI355X HBM3E, spec
 F32_MFMA_PEAK_FLOPS = 157.3e12  # MI355X v_mfma_f32_*_f32, spec
-
-
-def summary(times):
-    return {"median_s": statistics.median(times), "min_s": min(times), "max_s": max(times), "repeat": len(times)}
-
-
-def timed(fn, repeat, warmup, sync=None):
-    for _ in range(warmup):
-        fn()
-    if sync:
-        sync()
-    out = []
-    for _ in range(repeat):
-        t0 = time.perf_counter()
-        fn()
-        if sync:
-            sync()
-        out.append(time.perf_counter() - t0)
-    return summary(out)
 
 
 def torch_chunk(x, n_mels, padding, filters, window):
@@ -125,26 +105,15 @@ def main():
         p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
-        def launch():
+        def launch(i=0):
             rc = lib.wx_log_mel(p(wav), wav.numel(), host[0], host[1], host[2], p(ch_d), B, n_mels, p(filt), p(basis),
                                 p(out), audio.N_FRAMES, audio.N_FRAMES, p(ws), wsb, stream)
             assert rc == 0, rc
 
-        for _ in range(args.warmup):
-            launch()
+        launch()
         sync()
         assert torch.equal(out, ours)
-        times = []
-        for _ in range(args.repeat):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(args.steps):
-                launch()
-            e1.record()
-            sync()
-            times.append(e0.elapsed_time(e1) / 1e3 / args.steps)
-        k = summary(times)
-        k["steps"] = args.steps
+        k = event_timed(launch, args.repeat, args.warmup, args.steps, torch)
         k["algorithmic_bytes"] = int(length.sum()) * 4 + B * n_mels * audio.N_FRAMES * 4
         k["algorithmic_flop"] = audio_frames * (2 * 400 * 400 + 2 * 201 * n_mels)
         k["hbm_time_share"] = k["algorithmic_bytes"] / HBM_PEAK_BPS / k["median_s"]

@@ -27,60 +27,18 @@ from __future__ import annotations
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+from benchlib import beats, event_timed, timed  # noqa: E402
 
 HBM_PEAK_BYTES_PER_S = 8.0e12  # MI355X HBM3E, spec
 GEOMETRIES = {"base": {"D": 512, "layers": 6}, "large-v2": {"D": 1280, "layers": 32}}
 V, T, P = 51865, 448, 1500
 PROMPT = [50258, 50259, 50359]
 N_TOKENS, CHUNKS, STEP_POS = 64, 16, 35
-
-
-def summary(times):
-    return {"median_s": statistics.median(times), "min_s": min(times), "max_s": max(times), "repeat": len(times)}
-
-
-def timed(fn, repeat, warmup, sync):
-    for _ in range(warmup):
-        fn()
-    sync()
-    out = []
-    for _ in range(repeat):
-        t0 = time.perf_counter()
-        fn()
-        sync()
-        out.append(time.perf_counter() - t0)
-    return summary(out)
-
-
-def event_timed(fn, repeat, warmup, steps, torch):
-    """fn(i): launch number i of a repetition."""
-    for i in range(warmup):
-        fn(i)
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(repeat):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for i in range(steps):
-            fn(i)
-        e1.record()
-        torch.cuda.synchronize()
-        times.append(e0.elapsed_time(e1) / 1e3 / steps)
-    s = summary(times)
-    s["steps"] = steps
-    return s
-
-
-def beats(a, b):
-    return {"speedup_median": b["median_s"] / a["median_s"], "not_slower_median": bool(a["median_s"] <= b["median_s"]),
-            "beats_beyond_spread": bool(a["max_s"] < b["min_s"])}
 
 
 def attention_rows(D, args, torch, F, _lib, dev):

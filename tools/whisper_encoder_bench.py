@@ -23,58 +23,17 @@ from __future__ import annotations
 import argparse
 import json
 import os
-import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+from benchlib import beats, event_timed, timed  # noqa: E402
 
 F32_MFMA_PEAK_FLOPS = 157.3e12  # MI355X v_mfma_f32_*_f32, spec
 GEOMETRIES = {"base": {"D": 512, "layers": 6, "n_mels": 80, "chunks": 151},
               "large-v2": {"D": 1280, "layers": 32, "n_mels": 80, "chunks": 32}}
 P = 1500
-
-
-def summary(times):
-    return {"median_s": statistics.median(times), "min_s": min(times), "max_s": max(times), "repeat": len(times)}
-
-
-def timed(fn, repeat, warmup, sync):
-    for _ in range(warmup):
-        fn()
-    sync()
-    out = []
-    for _ in range(repeat):
-        t0 = time.perf_counter()
-        fn()
-        sync()
-        out.append(time.perf_counter() - t0)
-    return summary(out)
-
-
-def event_timed(fn, repeat, warmup, steps, torch):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(repeat):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(steps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        times.append(e0.elapsed_time(e1) / 1e3 / steps)
-    s = summary(times)
-    s["steps"] = steps
-    return s
-
-
-def beats(a, b):
-    return {"speedup_median": b["median_s"] / a["median_s"], "not_slower_median": bool(a["median_s"] <= b["median_s"]),
-            "beats_beyond_spread": bool(a["max_s"] < b["min_s"])}
 
 
 def main():
@@ -138,8 +97,8 @@ def main():
         out = torch.empty((nb, P, D), dtype=torch.float32, device=dev)
         with torch.inference_mode():
             r["max_abs_diff_stem_vs_torch"] = float((ours.stem(xb, out) - torch_stem(xb)).abs().max())
-            r["stem"] = event_timed(lambda: ours.stem(xb, out), args.repeat, args.warmup, args.steps, torch)
-            r["torch_stem"] = event_timed(lambda: torch_stem(xb), args.repeat, args.warmup, args.steps, torch)
+            r["stem"] = event_timed(lambda i: ours.stem(xb, out), args.repeat, args.warmup, args.steps, torch)
+            r["torch_stem"] = event_timed(lambda i: torch_stem(xb), args.repeat, args.warmup, args.steps, torch)
         r["stem"]["chunks"] = r["torch_stem"]["chunks"] = nb
         r["stem"]["algorithmic_flop"] = nb * (2 * 3 * M * D * 2 * P + 2 * 3 * D * D * P)
         r["stem"]["f32_mfma_time_share"] = r["stem"]["algorithmic_flop"] / F32_MFMA_PEAK_FLOPS / r["stem"]["median_s"]

@@ -27,7 +27,7 @@
 
 #include "wx_host.h"  // (and through it include/wx_align.h)
 
-namespace wxd {
+namespace wxdec {
 
 constexpr int kHead = 64;                       // head dim
 constexpr int kChunk = WX_DECODE_ATTENTION_CHUNK;  // keys per block
@@ -172,17 +172,17 @@ inline size_t carve(void* base, int32_t B, int32_t H, int32_t L, DecArgs* a) {
     return cv.off;
 }
 
-}  // namespace wxd
+}  // namespace wxdec
 
 extern "C" size_t wx_decode_attention_workspace_bytes(int32_t B, int32_t H, int32_t L) {
-    return wxd::carve(nullptr, B, H, L, nullptr);
+    return wxdec::carve(nullptr, B, H, L, nullptr);
 }
 
 extern "C" int wx_decode_attention_f32(const float* q, const float* k, const float* v, float* o, int32_t B, int32_t H,
                                        int32_t L, int32_t D, const int64_t* q_strides, const int64_t* k_strides,
                                        const int64_t* v_strides, float scale, void* workspace, size_t workspace_bytes,
                                        void* stream) {
-    using namespace wxd;
+    using namespace wxdec;
     if (B < 0 || H < 1 || L < 1 || D != kHead) return WX_E_INVALID;
     if (B == 0) return WX_OK;
     if (!q || !k || !v || !o || !q_strides || !k_strides || !v_strides || !workspace) return WX_E_INVALID;

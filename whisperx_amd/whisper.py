@@ -1,8 +1,9 @@
-"""Whisper's audio encoder (whisperx/asr.py:77-86, WhisperModel.encode) on the MI355X.
+"""Whisper's audio encoder and text decoder, run from their weights on the MI355X.
 
-The reference hands the log-mel features of its 30 s windows to CTranslate2; the arithmetic is
-transformers' `WhisperEncoder.forward` (fp32, eval, no mask), and that is what this module
-computes from the weights alone:
+The audio encoder (whisperx/asr.py:77-86, WhisperModel.encode): the reference hands the log-mel
+features of its 30 s windows to CTranslate2; the arithmetic is transformers'
+`WhisperEncoder.forward` (fp32, eval, no mask), and that is what this module computes from the
+weights alone:
 
     h = gelu(conv2(gelu(conv1(x)))) + pos                  wx_whisper_stem (one fused HIP stem)
     per layer:  y = LN1(h);  h = h + out(attn(q(y), k(y), v(y)))        one q/k/v GEMM, wx_attention_f32
@@ -26,58 +27,192 @@ Greedy decoding (beam_size 1, temperature 0) and language detection are built on
 temperature fallback, timestamps and the tokenizer are not.
 
 Without a GPU the same arithmetic runs in torch ops on the host (`F.conv1d`, `F.layer_norm`,
-`F.scaled_dot_product_attention`).
+`F.scaled_dot_product_attention`).  Both halves read their weights through one loader (`_Half`,
+`_Taker`) and run their layers as stages of one residual chain (`_chain`) on either route.
 """
 from __future__ import annotations
 
+import contextlib
 import re
-from typing import Optional
+import weakref
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
+from . import _lib
 from .audio import log_mel_chunks
 
 _LN_EPS = 1e-5
 
-# OpenAI's names (whisper/model.py AudioEncoder) -> transformers' (WhisperEncoder)
-_OPENAI_TOP = {"conv1": "conv1", "conv2": "conv2", "ln_post": "layer_norm"}
+
+# ---------------------------------------------------------------------- weights, for both halves
+class _Half(NamedTuple):
+    """What tells the encoder's weights from the decoder's."""
+    who: str         # the class, for messages
+    part: str        # `model.<part>.` / `<part>.` prefixes and module paths
+    other: tuple     # key prefixes of the rest of a model, dropped from a dict without a prefix
+    anchors: tuple   # a key starting with one of these (after the prefix) locates the prefix
+    has: tuple       # attributes by which the module is recognised
+    sniff: bool      # rename OpenAI's keys only when the dict looks like OpenAI's
+    top: dict        # OpenAI's top-level keys -> transformers'
+    block: dict      # OpenAI's names inside `blocks.N.` -> transformers' inside `layers.N.`
+    keep: Optional[str] = None  # a key beside this half that is kept under this name
+
+
+# OpenAI's names (whisper/model.py AudioEncoder, TextDecoder) -> transformers' (WhisperEncoder, WhisperDecoder)
 _OPENAI_BLOCK = {"attn.query": "self_attn.q_proj", "attn.key": "self_attn.k_proj", "attn.value": "self_attn.v_proj",
                  "attn.out": "self_attn.out_proj", "attn_ln": "self_attn_layer_norm", "mlp.0": "fc1", "mlp.2": "fc2",
                  "mlp_ln": "final_layer_norm"}
+_ENCODER = _Half("WhisperEncoder", "encoder", ("decoder.", "model.decoder.", "proj_out."), ("conv1.",),
+                 ("conv1", "embed_positions"), True,
+                 {"positional_embedding": "embed_positions.weight", "ln_post.weight": "layer_norm.weight",
+                  "ln_post.bias": "layer_norm.bias"}, _OPENAI_BLOCK)
+_DECODER = _Half("WhisperDecoder", "decoder", ("encoder.", "model.encoder."), ("embed_tokens.", "token_embedding."),
+                 ("embed_tokens", "embed_positions"), False,
+                 {"token_embedding.weight": "embed_tokens.weight", "positional_embedding": "embed_positions.weight",
+                  "ln.weight": "layer_norm.weight", "ln.bias": "layer_norm.bias"},
+                 {**_OPENAI_BLOCK, "cross_attn.query": "encoder_attn.q_proj", "cross_attn.key": "encoder_attn.k_proj",
+                  "cross_attn.value": "encoder_attn.v_proj", "cross_attn.out": "encoder_attn.out_proj",
+                  "cross_attn_ln": "encoder_attn_layer_norm"}, keep="proj_out.weight")
 
 
-def _hf_names(sd: dict) -> dict:
-    """A state dict under transformers' encoder names without a prefix: strips `model.encoder.` /
-    `encoder.`, and renames OpenAI's keys.  Keys of other parts of a model (the decoder) drop out."""
+def _hf_names(sd: dict, half: _Half) -> dict:
+    """A state dict under transformers' names of one half without a prefix: strips `model.<part>.` /
+    `<part>.`, and renames OpenAI's keys.  Keys of other parts of a model drop out, but for
+    `half.keep` (the decoder's `proj_out.weight`, under any of its spellings)."""
     keys = list(sd.keys())
-    openai = any(k.endswith("positional_embedding") or ".blocks." in k or k.startswith("blocks.") for k in keys)
-    for prefix in ("model.encoder.", "encoder.", ""):
-        if any(k.startswith(prefix + "conv1.") for k in keys):
+    rename = not half.sniff or any(k.endswith("positional_embedding") or ".blocks." in k or k.startswith("blocks.")
+                                   for k in keys)
+    for prefix in (f"model.{half.part}.", f"{half.part}.", ""):
+        if any(k.startswith(tuple(prefix + a for a in half.anchors)) for k in keys):
             break
     else:
-        raise ValueError("WhisperEncoder: the state dict has no conv1.weight (under 'model.encoder.', 'encoder.' or no prefix)")
+        raise ValueError(f"{half.who}: the state dict has no {' / '.join(a + 'weight' for a in half.anchors)} (under "
+                         f"'model.{half.part}.', '{half.part}.' or no prefix)")
     out = {}
     for k, v in sd.items():
+        if half.keep and k in (half.keep, "model." + half.keep, prefix + half.keep):
+            out[half.keep] = v
+            continue
         if not k.startswith(prefix):
             continue
         k = k[len(prefix):]
-        if prefix == "" and k.startswith(("decoder.", "model.decoder.", "proj_out.")):
+        if prefix == "" and k.startswith(half.other):
             continue
-        if openai:
-            if k == "positional_embedding":
-                k = "embed_positions.weight"
-            else:
-                m = re.match(r"blocks\.(\d+)\.(.+)\.(weight|bias)$", k)
-                if m and m.group(2) in _OPENAI_BLOCK:
-                    k = f"layers.{m.group(1)}.{_OPENAI_BLOCK[m.group(2)]}.{m.group(3)}"
-                else:
-                    m = re.match(r"(conv1|conv2|ln_post)\.(weight|bias)$", k)
-                    if m:
-                        k = f"{_OPENAI_TOP[m.group(1)]}.{m.group(2)}"
+        if rename:
+            m = re.match(r"blocks\.(\d+)\.(.+)\.(weight|bias)$", k)
+            if k in half.top:
+                k = half.top[k]
+            elif m and m.group(2) in half.block:
+                k = f"layers.{m.group(1)}.{half.block[m.group(2)]}.{m.group(3)}"
         out[k] = v
     return out
+
+
+def _state_dict(weights, half: _Half) -> dict:
+    """The tensors of one half under transformers' names, from a module (which is only read) or a
+    state dict."""
+    if isinstance(weights, dict):
+        return _hf_names(weights, half)
+    if not isinstance(weights, torch.nn.Module):
+        raise ValueError(f"{half.who}: weights must be a module or a state dict, not {type(weights).__name__}")
+    for path in (("model", half.part), (half.part,), ()):
+        mod = weights
+        for name in path:
+            mod = getattr(mod, name, None)
+        if mod is not None and all(hasattr(mod, a) for a in half.has):
+            break
+    else:
+        raise ValueError(f"{half.who}: the module has no Whisper {half.part} ({' / '.join(half.has)})")
+    sd = dict(mod.state_dict())
+    kept = getattr(getattr(weights, half.keep.split(".")[0], None), "weight", None) if half.keep else None
+    if kept is not None:
+        sd[half.keep] = kept
+    return sd
+
+
+def _device(device) -> torch.device:
+    """`device`, by default the current HIP device when one is visible, else the CPU; `cuda`
+    without an index is the current device."""
+    if device is None:
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+class _Taker:
+    """take(name, shape): tensor `name` of `sd` as contiguous fp32 on `device`, its shape checked;
+    every refusal is a ValueError that names the class and the tensor."""
+
+    def __init__(self, sd: dict, device: torch.device, who: str):
+        self.sd, self.device, self.who = sd, device, who
+
+    def __call__(self, name, shape=None):
+        t = self.sd.get(name)
+        if t is None:
+            raise ValueError(f"{self.who}: tensor '{name}' is missing")
+        t = t.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{self.who}: tensor '{name}' has shape {tuple(t.shape)}, expected {tuple(shape)}")
+        return t
+
+    def pair(self, prefix: str, n_out: int, n_in: Optional[int] = None):
+        """(weight, bias) of the LayerNorm (n_out) or Linear (n_out x n_in) under `prefix`."""
+        return self(prefix + ".weight", (n_out,) if n_in is None else (n_out, n_in)), self(prefix + ".bias", (n_out,))
+
+    def layer_prefixes(self) -> list:
+        """`layers.N.` for every layer of `sd`; the indices must be 0 .. n - 1."""
+        ids = sorted({int(m.group(1)) for m in (re.match(r"layers\.(\d+)\.", k) for k in self.sd) if m})
+        if ids != list(range(len(ids))):
+            raise ValueError(f"{self.who}: layer indices {ids} are not 0 .. n - 1")
+        return [f"layers.{i}." for i in ids]
+
+    def attention(self, p: str, D: int):
+        """The attention block under `p`: ([Wq; Wk; Wv] and its bias with a zero block for k, which
+        Whisper's k_proj does not have), (Wo, bo)."""
+        if self.sd.get(p + ".k_proj.bias") is not None:
+            raise ValueError(f"{self.who}: tensor '{p}.k_proj.bias' exists; Whisper's k_proj has no bias")
+        wq, wk, wv = (self(p + f".{n}_proj.weight", (D, D)) for n in "qkv")
+        bq, bv = self(p + ".q_proj.bias", (D,)), self(p + ".v_proj.bias", (D,))
+        return (torch.cat([wq, wk, wv], 0), torch.cat([bq, torch.zeros_like(bq), bv])), self.pair(p + ".out_proj", D, D)
+
+    def table(self, name: str, rows: str, D: int) -> torch.Tensor:
+        """A [rows, D] tensor whose row count is read from it."""
+        t = self(name)
+        if t.dim() != 2 or t.shape[1] != D:
+            raise ValueError(f"{self.who}: tensor '{name}' has shape {tuple(t.shape)}, expected [{rows}, {D}]")
+        return t
+
+    def mlp(self, p: str, D: int):
+        """fc1 and fc2 under the layer prefix `p`, the ffn width read from fc1."""
+        fc1 = self.table(p + "fc1.weight", "ffn", D)
+        ffn = int(fc1.shape[0])
+        return (fc1, self(p + "fc1.bias", (ffn,))), self.pair(p + "fc2", D, ffn)
+
+
+# ----------------------------------------------------------------- the residual stream, for both
+def _mlp(L: dict):
+    return lambda y: F.linear(F.gelu(F.linear(y, *L["fc1"])), *L["fc2"])
+
+
+def _chain(h: torch.Tensor, stages: list, final, add_norm=None) -> torch.Tensor:
+    """The pre-LN residual stream: h = h + fn(LN(h)) for every stage (ln, fn), then LN_final(h).
+    `ln` and `final` are (weight, bias) pairs.  With `add_norm` (_lib.add_layernorm on the HIP
+    route) every add is fused with the norm after it: the first norm has no residual to add and
+    is a plain layer_norm, the last add has no sum to keep."""
+    D = (h.shape[-1],)
+    if add_norm is None:
+        for ln, fn in stages:
+            h = h + fn(F.layer_norm(h, D, *ln, _LN_EPS))
+        return F.layer_norm(h, D, *final, _LN_EPS)
+    y = F.layer_norm(h, D, *(stages[0][0] if stages else final), _LN_EPS)
+    for (_, fn), (ln, _) in zip(stages, stages[1:]):
+        y, h = add_norm(h, fn(y), *ln, _LN_EPS, want_sum=True)
+    return add_norm(h, stages[-1][1](y), *final, _LN_EPS) if stages else y
 
 
 class WhisperEncoder:
@@ -93,37 +228,8 @@ class WhisperEncoder:
     current HIP device when one is visible, else the CPU)."""
 
     def __init__(self, weights, device=None):
-        if isinstance(weights, torch.nn.Module):
-            for path in ("model.encoder", "encoder", ""):
-                mod = weights
-                for name in filter(None, path.split(".")):
-                    mod = getattr(mod, name, None)
-                    if mod is None:
-                        break
-                if mod is not None and hasattr(mod, "conv1") and hasattr(mod, "embed_positions"):
-                    break
-            else:
-                raise ValueError("WhisperEncoder: the module has no Whisper encoder (conv1 / embed_positions)")
-            sd = {k: v for k, v in mod.state_dict().items()}
-        elif isinstance(weights, dict):
-            sd = _hf_names(weights)
-        else:
-            raise ValueError(f"WhisperEncoder: weights must be a module or a state dict, not {type(weights).__name__}")
-        if device is None:
-            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-
-        def take(name, shape=None):
-            t = sd.get(name)
-            if t is None:
-                raise ValueError(f"WhisperEncoder: tensor '{name}' is missing")
-            t = t.detach().to(device=self.device, dtype=torch.float32).contiguous()
-            if shape is not None and tuple(t.shape) != tuple(shape):
-                raise ValueError(f"WhisperEncoder: tensor '{name}' has shape {tuple(t.shape)}, expected {tuple(shape)}")
-            return t
-
+        self.device = _device(device)
+        take = _Taker(_state_dict(weights, _ENCODER), self.device, "WhisperEncoder")
         w1 = take("conv1.weight")
         if w1.dim() != 3 or w1.shape[2] != 3:
             raise ValueError(f"WhisperEncoder: tensor 'conv1.weight' has shape {tuple(w1.shape)}, expected [D, n_mels, 3]")
@@ -136,36 +242,16 @@ class WhisperEncoder:
         self.D, self.n_mels, self.H = D, M, D // 64
         self.w1, self.b1 = w1, take("conv1.bias", (D,))
         self.w2, self.b2 = take("conv2.weight", (D, D, 3)), take("conv2.bias", (D,))
-        self.pos = take("embed_positions.weight")
-        if self.pos.dim() != 2 or self.pos.shape[1] != D:
-            raise ValueError(f"WhisperEncoder: tensor 'embed_positions.weight' has shape {tuple(self.pos.shape)}, expected [P, {D}]")
+        self.pos = take.table("embed_positions.weight", "P", D)
         self.P = int(self.pos.shape[0])
-        ids = sorted({int(m.group(1)) for m in (re.match(r"layers\.(\d+)\.", k) for k in sd) if m})
-        if ids != list(range(len(ids))):
-            raise ValueError(f"WhisperEncoder: layer indices {ids} are not 0 .. n - 1")
         self.layers = []
-        for i in ids:
-            p = f"layers.{i}."
-            if sd.get(p + "self_attn.k_proj.bias") is not None:
-                raise ValueError(f"WhisperEncoder: tensor '{p}self_attn.k_proj.bias' exists; Whisper's k_proj has no bias")
-            fc1 = take(p + "fc1.weight")
-            if fc1.dim() != 2 or fc1.shape[1] != D:
-                raise ValueError(f"WhisperEncoder: tensor '{p}fc1.weight' has shape {tuple(fc1.shape)}, expected [ffn, {D}]")
-            ffn = int(fc1.shape[0])
-            wq, wk, wv = (take(p + f"self_attn.{n}_proj.weight", (D, D)) for n in "qkv")
-            bq, bv = take(p + "self_attn.q_proj.bias", (D,)), take(p + "self_attn.v_proj.bias", (D,))
-            self.layers.append({
-                "ln1": (take(p + "self_attn_layer_norm.weight", (D,)), take(p + "self_attn_layer_norm.bias", (D,))),
-                "qkv": (torch.cat([wq, wk, wv], 0).contiguous(), torch.cat([bq, torch.zeros_like(bq), bv]).contiguous()),
-                "out": (take(p + "self_attn.out_proj.weight", (D, D)), take(p + "self_attn.out_proj.bias", (D,))),
-                "ln2": (take(p + "final_layer_norm.weight", (D,)), take(p + "final_layer_norm.bias", (D,))),
-                "fc1": (fc1, take(p + "fc1.bias", (ffn,))),
-                "fc2": (take(p + "fc2.weight", (D, ffn)), take(p + "fc2.bias", (D,))),
-            })
-        self.ln_post = (take("layer_norm.weight", (D,)), take("layer_norm.bias", (D,)))
+        for p in take.layer_prefixes():
+            L = {"ln1": take.pair(p + "self_attn_layer_norm", D), "ln2": take.pair(p + "final_layer_norm", D)}
+            L["qkv"], L["out"] = take.attention(p + "self_attn", D)
+            L["fc1"], L["fc2"] = take.mlp(p, D)
+            self.layers.append(L)
+        self.ln_post = take.pair("layer_norm", D)
         if self.device.type == "cuda":
-            from . import _lib
-
             self.w1_packed = _lib.pack_conv3_weight(self.w1)
             self.w2_packed = _lib.pack_conv3_weight(self.w2)
 
@@ -196,13 +282,9 @@ class WhisperEncoder:
         kernel = self.device.type == "cuda"
         if kernel and x.stride(2) != 1 and x.shape[2] > 1:
             x = x.contiguous()
-        with torch.cuda.device(self.device) if kernel else _NullCtx():
+        with torch.cuda.device(self.device) if kernel else contextlib.nullcontext():
             for a in range(0, B, int(batch_size)):
-                xs, o = x[a:a + int(batch_size)], out[a:a + int(batch_size)]
-                if kernel:
-                    self._forward_kernels(xs, o)
-                else:
-                    o.copy_(self._forward_host(xs))
+                out[a:a + int(batch_size)].copy_(self._forward(x[a:a + int(batch_size)], kernel))
         return out
 
     def encode_chunks(self, audio, segments, n_mels: Optional[int] = None) -> torch.Tensor:
@@ -213,55 +295,36 @@ class WhisperEncoder:
 
     def stem(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The stem alone on the device: x [B, n_mels, 2 P] -> [B, P, D] (wx_whisper_stem)."""
-        from . import _lib
-
         return _lib.whisper_stem(x, self.w1_packed, self.b1, self.w2_packed, self.b2, self.pos, out)
 
-    def _forward_kernels(self, x: torch.Tensor, out: torch.Tensor) -> None:
-        """One slice on the HIP route, from the weights in the manner of emission._packed_layer."""
-        from . import _lib
-
-        B, P, D, H = int(x.shape[0]), self.P, self.D, self.H
-        s = self.stem(x).reshape(B * P, D)  # the residual stream
-        # (the first norm has no residual to add; every later one is fused with the add before it)
-        y = F.layer_norm(s, (D,), *(self.layers[0]["ln1"] if self.layers else self.ln_post), _LN_EPS)
-        for i, L in enumerate(self.layers):
-            qkv = F.linear(y, *L["qkv"])  # [B P, 3D]
-            q, k, v = (qkv[:, j * D:(j + 1) * D].view(B, P, H, 64).transpose(1, 2) for j in range(3))
-            o = _lib.attention_f32(q, k, v, 0.125).reshape(B * P, D)
-            o = F.linear(o, *L["out"])
-            y, s = _lib.add_layernorm(s, o, *L["ln2"], _LN_EPS, want_sum=True)
-            f = F.linear(F.gelu(F.linear(y, *L["fc1"])), *L["fc2"])
-            nxt = self.layers[i + 1]["ln1"] if i + 1 < len(self.layers) else self.ln_post
-            if i + 1 < len(self.layers):
-                y, s = _lib.add_layernorm(s, f, *nxt, _LN_EPS, want_sum=True)
-            else:
-                y = _lib.add_layernorm(s, f, *nxt, _LN_EPS)
-        out.copy_(y.view(B, P, D))
-
     def _forward_host(self, x: torch.Tensor) -> torch.Tensor:
-        """The same arithmetic in torch ops on x's device."""
+        """The host route's arithmetic on x's device (a HIP device too: the two routes are compared there)."""
+        return self._forward(x, False)
+
+    def _forward(self, x: torch.Tensor, kernel: bool) -> torch.Tensor:
+        """One slice [B, n_mels, 2 P] -> [B, P, D]: on the HIP route (stem, attention and the fused
+        add-norms are kernels, the residual stream is [B P, D]) or in torch ops on x's device."""
         B, P, D, H = int(x.shape[0]), self.P, self.D, self.H
-        h = F.gelu(F.conv1d(x, self.w1, self.b1, padding=1))
-        h = F.gelu(F.conv1d(h, self.w2, self.b2, stride=2, padding=1))
-        h = h.permute(0, 2, 1) + self.pos
-        for L in self.layers:
-            y = F.layer_norm(h, (D,), *L["ln1"], _LN_EPS)
-            qkv = F.linear(y, *L["qkv"])
+        if kernel:
+            h = self.stem(x).reshape(B * P, D)
+
+            def attend(q, k, v):
+                return _lib.attention_f32(q, k, v, 0.125).reshape(B * P, D)
+        else:
+            h = F.gelu(F.conv1d(x, self.w1, self.b1, padding=1))
+            h = F.gelu(F.conv1d(h, self.w2, self.b2, stride=2, padding=1))
+            h = h.permute(0, 2, 1) + self.pos
+
+            def attend(q, k, v):
+                return F.scaled_dot_product_attention(q, k, v, scale=0.125).transpose(1, 2).reshape(B, P, D)
+
+        def attention(y, L):
+            qkv = F.linear(y, *L["qkv"])  # [..., 3D]: one GEMM
             q, k, v = (qkv[..., j * D:(j + 1) * D].view(B, P, H, 64).transpose(1, 2) for j in range(3))
-            o = F.scaled_dot_product_attention(q, k, v, scale=0.125).transpose(1, 2).reshape(B, P, D)
-            h = h + F.linear(o, *L["out"])
-            y = F.layer_norm(h, (D,), *L["ln2"], _LN_EPS)
-            h = h + F.linear(F.gelu(F.linear(y, *L["fc1"])), *L["fc2"])
-        return F.layer_norm(h, (D,), *self.ln_post, _LN_EPS)
+            return F.linear(attend(q, k, v), *L["out"])
 
-
-class _NullCtx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
+        stages = [s for L in self.layers for s in ((L["ln1"], lambda y, L=L: attention(y, L)), (L["ln2"], _mlp(L)))]
+        return _chain(h, stages, self.ln_post, _lib.add_layernorm if kernel else None).view(B, P, D)
 
 
 def _load_state_dict(path: str, who: str) -> dict:
@@ -284,54 +347,17 @@ def load_whisper_encoder(path: str, device=None) -> WhisperEncoder:
 
 
 # ------------------------------------------------------------------------------------ decoder
-# OpenAI's names (whisper/model.py TextDecoder) -> transformers' (WhisperDecoder)
-_OPENAI_DEC_TOP = {"token_embedding.weight": "embed_tokens.weight", "positional_embedding": "embed_positions.weight",
-                   "ln.weight": "layer_norm.weight", "ln.bias": "layer_norm.bias"}
-_OPENAI_DEC_BLOCK = {**_OPENAI_BLOCK, "cross_attn.query": "encoder_attn.q_proj", "cross_attn.key": "encoder_attn.k_proj",
-                     "cross_attn.value": "encoder_attn.v_proj", "cross_attn.out": "encoder_attn.out_proj",
-                     "cross_attn_ln": "encoder_attn_layer_norm"}
-
-
-def _hf_decoder_names(sd: dict) -> dict:
-    """A state dict under transformers' decoder names without a prefix: strips `model.decoder.` /
-    `decoder.`, and renames OpenAI's keys.  Keys of other parts of a model (the encoder) drop out;
-    a `proj_out.weight` beside the decoder is kept under that name."""
-    keys = list(sd.keys())
-    for prefix in ("model.decoder.", "decoder.", ""):
-        if any(k.startswith((prefix + "embed_tokens.", prefix + "token_embedding.")) for k in keys):
-            break
-    else:
-        raise ValueError("WhisperDecoder: the state dict has no embed_tokens.weight / token_embedding.weight (under "
-                         "'model.decoder.', 'decoder.' or no prefix)")
-    out = {}
-    for k, v in sd.items():
-        if k in ("proj_out.weight", "model.proj_out.weight", prefix + "proj_out.weight"):
-            out["proj_out.weight"] = v
-            continue
-        if not k.startswith(prefix):
-            continue
-        k = k[len(prefix):]
-        if prefix == "" and k.startswith(("encoder.", "model.encoder.")):
-            continue
-        if k in _OPENAI_DEC_TOP:
-            k = _OPENAI_DEC_TOP[k]
-        else:
-            m = re.match(r"blocks\.(\d+)\.(.+)\.(weight|bias)$", k)
-            if m and m.group(2) in _OPENAI_DEC_BLOCK:
-                k = f"layers.{m.group(1)}.{_OPENAI_DEC_BLOCK[m.group(2)]}.{m.group(3)}"
-        out[k] = v
-    return out
-
-
 class DecoderState:
     """What `WhisperDecoder.start` returns and `step` advances: per layer the cross-attention keys
     and values (`cross`: [B, P, 2D], the k half then the v half of one GEMM), the self-attention
-    caches (`self_k` / `self_v`: [B, H, max_target_positions, 64]) and `pos`, the tokens so far."""
+    caches (`self_k` / `self_v`: [B, H, max_target_positions, 64]) and `pos`, the tokens so far.
+    `stages`: the decoder's layers bound to these tensors, built at the first step."""
 
     def __init__(self, B: int, P: int, cross, self_k, self_v, kernels: bool):
         self.B, self.P, self.pos = B, P, 0
         self.cross, self.self_k, self.self_v = cross, self_k, self_v
         self.kernels = kernels
+        self.stages = None
 
 
 class WhisperDecoder:
@@ -349,40 +375,8 @@ class WhisperDecoder:
     where the weights go (default: the current HIP device when one is visible, else the CPU)."""
 
     def __init__(self, weights, device=None):
-        if isinstance(weights, torch.nn.Module):
-            for path in ("model.decoder", "decoder", ""):
-                mod = weights
-                for name in filter(None, path.split(".")):
-                    mod = getattr(mod, name, None)
-                    if mod is None:
-                        break
-                if mod is not None and hasattr(mod, "embed_tokens") and hasattr(mod, "embed_positions"):
-                    break
-            else:
-                raise ValueError("WhisperDecoder: the module has no Whisper decoder (embed_tokens / embed_positions)")
-            sd = {k: v for k, v in mod.state_dict().items()}
-            proj = getattr(weights, "proj_out", None)
-            if proj is not None and getattr(proj, "weight", None) is not None:
-                sd["proj_out.weight"] = proj.weight
-        elif isinstance(weights, dict):
-            sd = _hf_decoder_names(weights)
-        else:
-            raise ValueError(f"WhisperDecoder: weights must be a module or a state dict, not {type(weights).__name__}")
-        if device is None:
-            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-
-        def take(name, shape=None):
-            t = sd.get(name)
-            if t is None:
-                raise ValueError(f"WhisperDecoder: tensor '{name}' is missing")
-            t = t.detach().to(device=self.device, dtype=torch.float32).contiguous()
-            if shape is not None and tuple(t.shape) != tuple(shape):
-                raise ValueError(f"WhisperDecoder: tensor '{name}' has shape {tuple(t.shape)}, expected {tuple(shape)}")
-            return t
-
+        self.device = _device(device)
+        take = _Taker(_state_dict(weights, _DECODER), self.device, "WhisperDecoder")
         self.embed = take("embed_tokens.weight")
         if self.embed.dim() != 2:
             raise ValueError(f"WhisperDecoder: tensor 'embed_tokens.weight' has shape {tuple(self.embed.shape)}, expected [V, D]")
@@ -391,51 +385,25 @@ class WhisperDecoder:
             raise ValueError(f"WhisperDecoder: tensor 'embed_tokens.weight' has width {D}; the model width must be a "
                              "multiple of the head size 64, at most 1280")
         self.V, self.D, self.H = V, D, D // 64
-        if sd.get("proj_out.weight") is not None and not torch.equal(take("proj_out.weight", (V, D)), self.embed):
+        if take.sd.get("proj_out.weight") is not None and not torch.equal(take("proj_out.weight", (V, D)), self.embed):
             raise ValueError("WhisperDecoder: tensor 'proj_out.weight' differs from embed_tokens.weight; the output "
                              "projection must be tied to the token embedding")
-        self.pos = take("embed_positions.weight")
-        if self.pos.dim() != 2 or self.pos.shape[1] != D:
-            raise ValueError(f"WhisperDecoder: tensor 'embed_positions.weight' has shape {tuple(self.pos.shape)}, expected [T, {D}]")
+        self.pos = take.table("embed_positions.weight", "T", D)
         self.max_target_positions = int(self.pos.shape[0])
-        ids = sorted({int(m.group(1)) for m in (re.match(r"layers\.(\d+)\.", k) for k in sd) if m})
-        if ids != list(range(len(ids))):
-            raise ValueError(f"WhisperDecoder: layer indices {ids} are not 0 .. n - 1")
         self.layers = []
-        for i in ids:
-            p = f"layers.{i}."
-            for a in ("self_attn", "encoder_attn"):
-                if sd.get(p + a + ".k_proj.bias") is not None:
-                    raise ValueError(f"WhisperDecoder: tensor '{p}{a}.k_proj.bias' exists; Whisper's k_proj has no bias")
-            fc1 = take(p + "fc1.weight")
-            if fc1.dim() != 2 or fc1.shape[1] != D:
-                raise ValueError(f"WhisperDecoder: tensor '{p}fc1.weight' has shape {tuple(fc1.shape)}, expected [ffn, {D}]")
-            ffn = int(fc1.shape[0])
-            wq, wk, wv = (take(p + f"self_attn.{n}_proj.weight", (D, D)) for n in "qkv")
-            bq, bv = take(p + "self_attn.q_proj.bias", (D,)), take(p + "self_attn.v_proj.bias", (D,))
-            xk, xv = take(p + "encoder_attn.k_proj.weight", (D, D)), take(p + "encoder_attn.v_proj.weight", (D, D))
-            xbv = take(p + "encoder_attn.v_proj.bias", (D,))
-
-            def ln(name, p=p):
-                return take(p + name + ".weight", (D,)), take(p + name + ".bias", (D,))
-
-            self.layers.append({
-                "ln1": ln("self_attn_layer_norm"),
-                "qkv": (torch.cat([wq, wk, wv], 0).contiguous(), torch.cat([bq, torch.zeros_like(bq), bv]).contiguous()),
-                "out": (take(p + "self_attn.out_proj.weight", (D, D)), take(p + "self_attn.out_proj.bias", (D,))),
-                "ln2": ln("encoder_attn_layer_norm"),
-                "q_x": (take(p + "encoder_attn.q_proj.weight", (D, D)), take(p + "encoder_attn.q_proj.bias", (D,))),
-                "kv_x": (torch.cat([xk, xv], 0).contiguous(), torch.cat([torch.zeros_like(xbv), xbv]).contiguous()),
-                "out_x": (take(p + "encoder_attn.out_proj.weight", (D, D)), take(p + "encoder_attn.out_proj.bias", (D,))),
-                "ln3": ln("final_layer_norm"),
-                "fc1": (fc1, take(p + "fc1.bias", (ffn,))),
-                "fc2": (take(p + "fc2.weight", (D, ffn)), take(p + "fc2.bias", (D,))),
-            })
-        self.ln_f = (take("layer_norm.weight", (D,)), take("layer_norm.bias", (D,)))
+        for p in take.layer_prefixes():
+            L = {"ln1": take.pair(p + "self_attn_layer_norm", D), "ln2": take.pair(p + "encoder_attn_layer_norm", D),
+                 "ln3": take.pair(p + "final_layer_norm", D)}
+            L["qkv"], L["out"] = take.attention(p + "self_attn", D)
+            (w, b), L["out_x"] = take.attention(p + "encoder_attn", D)
+            L["q_x"], L["kv_x"] = (w[:D], b[:D]), (w[D:], b[D:])  # q per step; [Wk_x; Wv_x] once, in start()
+            L["fc1"], L["fc2"] = take.mlp(p, D)
+            self.layers.append(L)
+        self.ln_f = take.pair("layer_norm", D)
 
     # --------------------------------------------------------------------------------- steps
     def _ctx(self):
-        return torch.cuda.device(self.device) if self.device.type == "cuda" else _NullCtx()
+        return torch.cuda.device(self.device) if self.device.type == "cuda" else contextlib.nullcontext()
 
     @torch.inference_mode()
     def start(self, encoder_states: torch.Tensor, kernels: Optional[bool] = None) -> DecoderState:
@@ -481,53 +449,42 @@ class WhisperDecoder:
         if st.pos >= self.max_target_positions:
             raise ValueError(f"WhisperDecoder.step: position {st.pos} is past max_target_positions "
                              f"({self.max_target_positions})")
+        if st.stages is None:  # once per state: the step path only calls them
+            st.stages = self._stages(weakref.proxy(st))  # (a proxy: the state owns its stages, not they it)
         with self._ctx():
             h = F.embedding(tok, self.embed) + self.pos[st.pos]
-            y = self._layers_kernels(st, h) if st.kernels else self._layers_host(st, h)
+            y = _chain(h, st.stages, self.ln_f, _lib.add_layernorm if st.kernels else None)
             st.pos += 1
             return F.linear(y, self.embed)
 
-    def _layers_kernels(self, st: DecoderState, s: torch.Tensor) -> torch.Tensor:
-        """LN_f of the residual stream after every layer, on the HIP route: both attentions on
-        wx_decode_attention_f32, every residual add fused with the norm after it."""
-        from . import _lib
+    def _stages(self, st: DecoderState) -> list:
+        """The three stages of every layer on the state's tensors and route, at the position the
+        state is at when they are called: both attentions on wx_decode_attention_f32 or on
+        torch's; the first writes the cache rows."""
+        B, P, D, H = st.B, st.P, self.D, self.H
+        if st.kernels:
+            def attend(q, k, v, n=None):
+                return _lib.decode_attention_f32(q, k, v, 0.125, L=n).view(B, D)
+        else:
+            def attend(q, k, v, n=None):
+                return F.scaled_dot_product_attention(q.unsqueeze(2), k[:, :, :n], v[:, :, :n], scale=0.125).reshape(B, D)
 
-        B, D, H, n, pos = st.B, self.D, self.H, len(self.layers), st.pos
-        y = F.layer_norm(s, (D,), *(self.layers[0]["ln1"] if n else self.ln_f), _LN_EPS)
-        for i, L in enumerate(self.layers):
-            qkv = F.linear(y, *L["qkv"])  # [B, 3D]
-            q, k, v = (qkv[:, j * D:(j + 1) * D].view(B, H, 64) for j in range(3))
-            st.self_k[i][:, :, pos].copy_(k)
-            st.self_v[i][:, :, pos].copy_(v)
-            o = _lib.decode_attention_f32(q, st.self_k[i], st.self_v[i], 0.125, L=pos + 1).view(B, D)
-            y, s = _lib.add_layernorm(s, F.linear(o, *L["out"]), *L["ln2"], _LN_EPS, want_sum=True)
-            kx, vx = (st.cross[i][:, :, j * D:(j + 1) * D].view(B, st.P, H, 64).transpose(1, 2) for j in range(2))
-            o = _lib.decode_attention_f32(F.linear(y, *L["q_x"]).view(B, H, 64), kx, vx, 0.125).view(B, D)
-            y, s = _lib.add_layernorm(s, F.linear(o, *L["out_x"]), *L["ln3"], _LN_EPS, want_sum=True)
-            f = F.linear(F.gelu(F.linear(y, *L["fc1"])), *L["fc2"])
-            if i + 1 < n:
-                y, s = _lib.add_layernorm(s, f, *self.layers[i + 1]["ln1"], _LN_EPS, want_sum=True)
-            else:
-                y = _lib.add_layernorm(s, f, *self.ln_f, _LN_EPS)
-        return y
+        def self_attention(L, ck, cv):
+            def fn(y):
+                pos = st.pos
+                qkv = F.linear(y, *L["qkv"])  # [B, 3D]
+                q, k, v = (qkv[:, j * D:(j + 1) * D].view(B, H, 64) for j in range(3))
+                ck[:, :, pos].copy_(k)
+                cv[:, :, pos].copy_(v)
+                return F.linear(attend(q, ck, cv, pos + 1), *L["out"])
+            return fn
 
-    def _layers_host(self, st: DecoderState, h: torch.Tensor) -> torch.Tensor:
-        """The same arithmetic in torch ops on the state's device."""
-        B, D, H, pos = st.B, self.D, self.H, st.pos
-        for i, L in enumerate(self.layers):
-            qkv = F.linear(F.layer_norm(h, (D,), *L["ln1"], _LN_EPS), *L["qkv"])
-            q, k, v = (qkv[:, j * D:(j + 1) * D].view(B, H, 64) for j in range(3))
-            st.self_k[i][:, :, pos].copy_(k)
-            st.self_v[i][:, :, pos].copy_(v)
-            o = F.scaled_dot_product_attention(q.unsqueeze(2), st.self_k[i][:, :, :pos + 1], st.self_v[i][:, :, :pos + 1],
-                                               scale=0.125).reshape(B, D)
-            h = h + F.linear(o, *L["out"])
-            q = F.linear(F.layer_norm(h, (D,), *L["ln2"], _LN_EPS), *L["q_x"]).view(B, H, 1, 64)
-            kx, vx = (st.cross[i][:, :, j * D:(j + 1) * D].view(B, st.P, H, 64).transpose(1, 2) for j in range(2))
-            o = F.scaled_dot_product_attention(q, kx, vx, scale=0.125).reshape(B, D)
-            h = h + F.linear(o, *L["out_x"])
-            h = h + F.linear(F.gelu(F.linear(F.layer_norm(h, (D,), *L["ln3"], _LN_EPS), *L["fc1"])), *L["fc2"])
-        return F.layer_norm(h, (D,), *self.ln_f, _LN_EPS)
+        def cross_attention(L, kv):
+            kx, vx = (kv[:, :, j * D:(j + 1) * D].view(B, P, H, 64).transpose(1, 2) for j in range(2))  # views, in place
+            return lambda y: F.linear(attend(F.linear(y, *L["q_x"]).view(B, H, 64), kx, vx), *L["out_x"])
+
+        return [s for L, kv, ck, cv in zip(self.layers, st.cross, st.self_k, st.self_v)
+                for s in ((L["ln1"], self_attention(L, ck, cv)), (L["ln2"], cross_attention(L, kv)), (L["ln3"], _mlp(L)))]
 
     @torch.inference_mode()
     def logits(self, encoder_states: torch.Tensor, tokens, kernels: Optional[bool] = None) -> torch.Tensor:
