@@ -54,8 +54,13 @@ namespace wx {
 // its own launch's epoch in the same high half.  (Round 2 matched 24 epoch bits of a 4-byte
 // word, which a granule's float half could match by chance.)  Returns the low word after
 // this arrival.
-__device__ unsigned split_arrive(uint64_t* c, unsigned epoch, bool lost) {
-    uint64_t old = __hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+// One round trip in the steady state: the CAS loop starts from a guessed word instead of a
+// load — {epoch, part} for part > 0 (parts arrive in order when nothing is lost), the zero word
+// for part 0 (the last part of the launch before reset the counter).  A wrong guess changes
+// nothing: the CAS fails, returns the word that is there, and the loop goes on from it as it
+// would from a load.
+__device__ unsigned split_arrive(uint64_t* c, unsigned epoch, bool lost, int part) {
+    uint64_t old = part > 0 ? (((uint64_t)epoch << 32) | (unsigned)part) : (uint64_t)0;
     while (true) {
         const unsigned cur = ((unsigned)(old >> 32) == epoch) ? (unsigned)old : 0u;
         const unsigned nw = ((cur & 0x7Fu) + 1u) | (cur & 0x80u) | (lost ? 0x80u : 0u);
@@ -199,7 +204,7 @@ __device__ __forceinline__ void align_dp_body(const AlignArgs& a) {
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
                 wait_vm();
             }
-            const unsigned w = split_arrive(a.arrive + seg, a.epoch, tsb[2] != 0);
+            const unsigned w = split_arrive(a.arrive + seg, a.epoch, tsb[2] != 0, part);
             tsb[0] = ((w & 0x7Fu) == (unsigned)P) ? 1 + (int)((w >> 7) & 1u) : 0;
             if (tsb[0]) {
                 if (fenced) {  // (WT: the walk reads the parts' words with sc1 loads)

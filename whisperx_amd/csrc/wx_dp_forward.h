@@ -285,6 +285,12 @@ struct Forward {
         Geo::owner(L.G - 1, own_w, own_l);
         const bool owner = uniform(own_w) == vw && l == own_l;
         const bool owner_wave = uniform(own_w) == vw;
+        if constexpr (kReg) {  // the register-resident split forward has its own chunk loop
+            const int etq = (vw == 0 && l == 0) ? VS * 16 : toff[0] * 4;  // quad byte offset of this lane's column
+            const int ebq = boff * 4;                                      // ... of the blank (uniform)
+            reg_forward(sp, lds, xh, bits, cn, nch, T, wv, g, L.G, halo, xpub, xsub, owner, owner_wave, etq, ebq);
+            return false;  // (a lost hand-off is the poller's to report: helper_reg)
+        }
 
         State st;
         if (MODE == 1) {
@@ -340,17 +346,7 @@ struct Forward {
 #pragma unroll
             for (int k = 0; k < C; ++k) st_pub<kWT>(bits + ((int64_t)qd * C + k) * lanes + g, wdef[k]);
         };
-        // kReg: the operands of the chunk being computed (o) and of the next one (n), swapped
-        // by the two-way unrolled chunk loop
-        RegOps opsA, opsB;
-        const int etq = (vw == 0 && l == 0) ? VS * 16 : toff[0] * 4;  // quad byte offset of this lane's column
-        const int ebq = boff * 4;                                      // ... of the blank (uniform)
-        if (kReg) __syncthreads();  // barrier -1 (helper_reg: the column-0 helper's first two chunks)
-        // OWN (compile time): the wave holding column N (the only one with column-N stores; the
-        // others have no branch around them: a taken branch per eight steps cost the DP waves
-        // ~20% of their step time).
-        auto chunk_iter = [&](const int q, uint64_t(&xpre)[C], RegOps& o, RegOps& n, auto own) {
-            constexpr bool OWN = decltype(own)::value;
+        auto chunk_iter = [&](const int q, uint64_t(&xpre)[C]) {
             WX_T(c0);
             float* buf = lds + (q % kBufs) * kBufFloats;
             const int rows = min(kChunk, T - q * kChunk);
@@ -377,9 +373,7 @@ struct Forward {
 #pragma unroll
                 for (int k = 0; k < C; ++k) st.cur[k] = xq[(wv - 1) * kWave + l * C + k];
             }
-            if (kReg && SP && xsub && q > 0) {  // (the poller's values: Split::xg)
-                if (l < Geo::HL) st.cur[0] = sp->xg[(q & 1) * 32 + l];
-            } else if (SP && xsub && q > 0) {
+            if (SP && xsub && q > 0) {
                 // Halo of row 32q from the previous part: the granules prefetched two chunks
                 // ago (the sc1 load takes longer than a chunk).  A part must trail its
                 // predecessor by more than the prefetch distance plus the hand-off latency for
@@ -435,26 +429,10 @@ struct Forward {
             const char* bb = reinterpret_cast<const char*>(buf);
             const float* c0q = kC0Lds ? c0b + (q & 1) * kChunk : nullptr;
             WX_T(c3);
-            if constexpr (kReg) {
-                if (q == 0) reg_load(o, bb, etq, ebq);
-                // the next chunk's operands (the last chunk re-reads its own rows: harmless)
-                const char* nb = reinterpret_cast<const char*>(lds + ((q + 1 < nch ? q + 1 : q) % kBufs) * kBufFloats);
-                float cur0 = st.cur[0];
-                reg_chunk<OWN>(o, n, nb, etq, ebq, cur0, st.w[0], owner, cn, q * kChunk, T);
-                // Invariant: on a partial last chunk reg_chunk runs all 32 steps on stale rows,
-                // so st.cur then holds the cell 32 steps on, not `rows` steps: nothing reads the
-                // state after the last chunk (its bits are masked below, column N stops at T).
-                // A change that publishes or reads the final cell state must keep
-                // hist[(rows - 1) & 7] instead.
-                st.cur[0] = cur0;
-                st.t += rows;
+            if (vw == 0) {
+                chunk<true>(bb, c0q, rows, toff, boff, st, inf_from, is_short, halo, f, cnt, owner, N, cn, tr);
             } else {
-                (void)OWN;
-                if (vw == 0) {
-                    chunk<true>(bb, c0q, rows, toff, boff, st, inf_from, is_short, halo, f, cnt, owner, N, cn, tr);
-                } else {
-                    chunk<false>(bb, c0q, rows, toff, boff, st, inf_from, is_short, halo, f, cnt, owner, N, cn, tr);
-                }
+                chunk<false>(bb, c0q, rows, toff, boff, st, inf_from, is_short, halo, f, cnt, owner, N, cn, tr);
             }
             if (c0prod && q + 1 < nch) c0_make(q + 1, c0e);  // (read after barrier q + 1)
             WX_T(c4);
@@ -465,10 +443,7 @@ struct Forward {
                 const int sh = kChunk - rows;  // keep bit 31 = first step of the block
 #pragma unroll
                 for (int k = 0; k < C; ++k) {
-                    // (kReg runs all 32 steps of a partial chunk: bit 31 is already the first
-                    // step, the bits of the steps past T are dropped)
-                    const unsigned wq = kReg ? (st.w[k] & (0xFFFFFFFFu << sh))
-                                             : ((sh == 0) ? st.w[k] : (st.w[k] << sh));
+                    const unsigned wq = (sh == 0) ? st.w[k] : (st.w[k] << sh);
                     if (SP)
                         wdef[k] = wq;
                     else if (!halo && g < L.G)  // (lanes past column N: words the walk never reads)
@@ -478,19 +453,13 @@ struct Forward {
             }
         };
         if constexpr (SP) {
-            auto loop = [&](auto own) {
-                for (int q = 0; q < nch; q += 2) {
-                    chunk_iter(q, xeven, opsA, opsB, own);
-                    if (q + 1 < nch) chunk_iter(q + 1, xodd, opsB, opsA, own);
-                }
-            };
-            if (owner_wave)
-                loop(BoolTag<true>{});
-            else
-                loop(BoolTag<false>{});
+            for (int q = 0; q < nch; q += 2) {
+                chunk_iter(q, xeven);
+                if (q + 1 < nch) chunk_iter(q + 1, xodd);
+            }
             if (MODE == 0 && nch > 0 && !halo && g < L.G) store_deferred(nch - 1);
         } else {
-            for (int q = 0; q < nch; ++q) chunk_iter(q, xeven, opsA, opsB, BoolTag<true>{});
+            for (int q = 0; q < nch; ++q) chunk_iter(q, xeven);
         }
         WX_TDUMP(l == 0 && MODE != 1, wv, acc_steps, acc_bar, acc_other,
                  if (SP && xsub) { WX_TSTORE(14, x_miss, x_wait, x_slack) });
@@ -544,14 +513,11 @@ struct Forward {
 #undef WX_REG_OPERANDS
 #undef WX_REG_STEP
     // 32 steps on operands `o`, issuing the next chunk's operand reads (n, from buffer nb) one
-    // quad ahead of each group of four steps; column N history stored by the owner lane (rows
-    // past T skipped: the steps of a partial chunk past T compute on stale rows, harmlessly).
-    // OWN: this wave holds column N (the others have no column-N code)
+    // quad ahead of each group of four steps.  OWN: this wave holds column N (the others have
+    // no column-N code); hist: the cell value after each step, which reg_forward stores.
     template <bool OWN>
     __device__ __forceinline__ static void reg_chunk(const RegOps& o, RegOps& n, const char* nb, int etq, int ebq,
-                                                     float& cur, unsigned& w, bool owner, float* __restrict__ cn,
-                                                     int t0, int T) {
-        float hist[OWN ? kChunk : 1];
+                                                     float& cur, unsigned& w, float (&hist)[OWN ? kChunk : 1]) {
 #pragma unroll
         for (int p = 0; p < kChunk / 4; ++p) {
             n.et[p] = *reinterpret_cast<const float4*>(nb + p * kQS * 4 + etq);
@@ -569,18 +535,124 @@ struct Forward {
             cur = nv[3];
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (OWN && owner) {
-            // rows t0 + 1 .. t0 + 32 -> cn[t0 .. t0 + 31], once per chunk and whole: rows past T
-            // land in the segment's padding (kCnPad).  (Stored per 8 steps inside the chain,
-            // with a partial-group path, they cost the pacing wave a taken branch and an EXEC
-            // round trip per 8 steps: 59.7 -> 55.3 -> ... us.)
-            // Eight 16-byte stores, written through (sc1, kWT): the last part reads them with
-            // sc1 loads and the arrival needs no release (32 single 4-byte sc1 stores had cost
-            // more than the release).
+    }
+
+    // The DP waves' chunk loop of the register-resident split forward (run() sends them here;
+    // C = 1, so a lane is one cell and HL = 32 halo lanes).  Per chunk q: barrier q; the halo of
+    // row 32 q comes in; chunk q - 1's decision word goes out (one chunk late, as in run());
+    // the 32 steps (reg_chunk), which also read chunk q + 1's operands; then row 32 (q + 1) is
+    // published for barrier q + 1 — to the next wave through xh, to the next part as granules —
+    // and the owner lane stores the chunk's column-N history.
+    // Barriers: every DP wave that comes here executes barrier -1 and then exactly one barrier per
+    // chunk, nch in all (iter() has the only __syncthreads of the loop and is called once for
+    // every q in [0, nch)), which is what run()'s other routes — helpers, extra walker waves,
+    // waves without a column — execute.  Nothing here waits, polls or sleeps.
+    // What sits between two chunks' steps is kept short (it is paid 47 times by every wave of
+    // config 2, on the chain through the parts):
+    //   * chunk 0 and the two parities are separate copies (FIRST, PAR), the ring slot is a
+    //     running byte offset, pointers advance by their strides: nothing is derived from q;
+    //   * the two LDS accesses have no branch and no wave condition: every lane writes (the
+    //     lanes that publish nothing into a pad slot of their wave's xh row, slots 32..63 of
+    //     each 64: a C = 1 halo fills only 0..31), and every wave reads through one pointer pair
+    //     set up here — the previous wave's row, the poller's Split::xg or, in the column-1 wave,
+    //     its own row — and keeps the value in its halo lanes only (a select; hipcc makes it one
+    //     ds_read under the halo lanes' mask);
+    //   * the publish is issued directly behind the last step, so its LDS latency runs under
+    //     the rest of the boundary;
+    //   * a partial last chunk runs all 32 steps on stale rows (harmless: nothing reads the
+    //     cell state after the last chunk, and column N's rows past T land in the padding);
+    //     the bits of its steps past T are dropped from its word once, after the loop.
+    __device__ __forceinline__ static void reg_forward(const Split* sp, float* lds, float* xh,
+                                                       unsigned* __restrict__ bits, float* __restrict__ cn, int nch,
+                                                       int T, int wv, int g, int G, bool halo, bool xpub,
+                                                       bool xsub, bool owner, bool owner_wave, int etq, int ebq) {
+        constexpr int HL = Geo::HL;
+        static_assert(C == 1 && 2 * HL == kWave, "pad slots: a C = 1 halo fills half of a wave's xh row");
+        const int l = lane_id();
+        const int lanes = sp->lanes;
+        constexpr int kBufBytes = kBufFloats * 4;
+        // LDS: where this lane publishes (chunk parity 0; parity 1 is W * kWave floats on) ...
+        float* const hw = xh + wv * kWave + (l ^ HL);  // lanes >= 32: slots 0..31; the others: pad
+        // ... and where its halo value of an even / odd chunk arrives: the previous wave's row,
+        // or (wave 0 of a part > 0) the poller's Split::xg; the column-1 wave reads its own row
+        const float* hr[2];
+        hr[0] = (wv > 0 ? xh + (wv - 1) * kWave : (xsub ? sp->xg : xh)) + (l & (HL - 1));
+        hr[1] = hr[0] + ((wv > 0 || !xsub) ? W * kWave : 32);
+        const bool own_word = !halo && g < G;                         // lanes whose decision word is kept
+        unsigned* wp = bits + ((int64_t)g - lanes);                   // chunk q - 1's word
+        uint64_t* gp = sp->xout + (l - (kWave - HL));                 // chunk q's granule (lanes >= 32)
+        int t0 = 0;                                                   // column N: rows t0 + 1 .. t0 + 32
+        int rn = kBufBytes;                                           // ring byte offset of chunk q + 1
+        float cur = -INFINITY;                                        // row 0, columns 1..N
+        unsigned w = 0u, wdef = 0u;                                   // this chunk's word, the last one's
+        RegOps opsA, opsB;  // the operands of the chunk being computed and of the next one, swapped per chunk
+        WX_TDECL(acc_steps = 0, acc_bar = 0, acc_other = 0);
+        __syncthreads();  // barrier -1 (helper_reg: the column-0 helper's first two chunks)
+        // OWN (compile time): the wave holding column N (the only one with column-N stores; the
+        // others have no branch around them: a taken branch per eight steps cost the DP waves
+        // ~20% of their step time).
+        auto iter = [&](const int q, auto first, auto par, RegOps& o, RegOps& n, auto own) {
+            constexpr bool FIRST = decltype(first)::value, OWN = decltype(own)::value;
+            constexpr int PAR = decltype(par)::value ? 1 : 0;
+            WX_T(c1);
+            __syncthreads();  // barrier q
+            WX_T(c2);
+            if (wv == 0) { WX_CQ(q, 0); }
+            if constexpr (FIRST) {
+                reg_load(o, reinterpret_cast<const char*>(lds), etq, ebq);
+            } else {
+                const float hv = *hr[PAR];
+                cur = halo ? hv : cur;
+                if (own_word) st_pub<kWT>(wp, wdef);
+            }
+            wp += lanes;
+            const char* nb = reinterpret_cast<const char*>(lds) + rn;
+            rn = rn + kBufBytes == kBufs * kBufBytes ? 0 : rn + kBufBytes;
+            WX_T(c3);
+            float hist[OWN ? kChunk : 1];
+            reg_chunk<OWN>(o, n, nb, etq, ebq, cur, w, hist);
+            WX_T(c4);
+            hw[(PAR ^ 1) * W * kWave] = cur;  // (every lane writes; after the last chunk: read by no one)
+            gp += sp->xstride;
+            if (xpub && q + 1 < nch) {
+                if (l >= kWave - HL) granule_store(gp, cur, sp->tag);
+                WX_CQ(q + 1, 1);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            if (OWN && owner) {
+                // rows t0 + 1 .. t0 + 32 -> cn[t0 .. t0 + 31], once per chunk and whole: rows past T
+                // land in the segment's padding (kCnPad).  (Stored per 8 steps inside the chain,
+                // with a partial-group path, they cost the pacing wave a taken branch and an EXEC
+                // round trip per 8 steps: 59.7 -> 55.3 -> ... us.)
+                // Eight 16-byte stores, written through (sc1, kWT): the last part reads them with
+                // sc1 loads and the arrival needs no release (32 single 4-byte sc1 stores had cost
+                // more than the release).
 #pragma unroll
-            for (int i = 0; i < kChunk / 4; ++i)
-                st_pub4<kWT>(cn, t0 + 4 * i, make_float4(hist[4 * i], hist[4 * i + 1], hist[4 * i + 2], hist[4 * i + 3]));
-        }
+                for (int i = 0; i < kChunk / 4; ++i)
+                    st_pub4<kWT>(cn, t0 + 4 * i, make_float4(hist[4 * i], hist[4 * i + 1], hist[4 * i + 2], hist[4 * i + 3]));
+            }
+            t0 += kChunk;
+            wdef = w;
+            w = 0u;
+            WX_T(c5);
+            WX_TACC(acc_steps, c4 - c3);
+            WX_TACC(acc_bar, c2 - c1);
+            WX_TACC(acc_other, (c3 - c2) + (c5 - c4));
+        };
+        auto loop = [&](auto own) {
+            if (nch > 0) iter(0, BoolTag<true>{}, BoolTag<false>{}, opsA, opsB, own);
+            for (int q = 1; q < nch; q += 2) {
+                iter(q, BoolTag<false>{}, BoolTag<true>{}, opsB, opsA, own);
+                if (q + 1 < nch) iter(q + 1, BoolTag<false>{}, BoolTag<false>{}, opsA, opsB, own);
+            }
+        };
+        if (owner_wave)
+            loop(BoolTag<true>{});
+        else
+            loop(BoolTag<false>{});
+        // the last chunk's word: bit 31 is its first step, the bits of the steps past T are dropped
+        if (nch > 0 && own_word) st_pub<kWT>(wp, wdef & (0xFFFFFFFFu << (nch * kChunk - T)));
+        WX_TDUMP(l == 0, wv, acc_steps, acc_bar, acc_other, if (xsub) { WX_TSTORE(14, 0, 0, 0) });
     }
 
     // Helper waves: the waves beyond the W DP waves (run() sends them here; they keep its barrier count): helper (H),
