@@ -243,8 +243,9 @@ int wx_channel_norm(const float* x, int64_t L, int32_t C, const float* gamma, co
  * GroupNorm with one group per channel (statistics over time in fp64, biased variance, affine
  * gamma / beta, eps) and act the exact erf GELU when gelu != 0 (identity otherwise).  y is
  * [Lout, C] time-major, Lout = (S - K) / stride + 1.  The convolution is recomputed in the
- * second pass instead of being stored.  Equal to torch's conv + GroupNorm + GELU to fp32
- * tolerance (its own summation order). */
+ * second pass instead of being stored.  A per-channel constant cancels in the per-channel
+ * normalisation, so bias is accepted and never read.  Equal to torch's conv + GroupNorm + GELU to
+ * fp32 tolerance (its own summation order). */
 size_t wx_conv0_channel_norm_workspace_bytes(int64_t L, int32_t C);
 int wx_conv0_channel_norm(const float* x, int64_t S, int32_t K, int32_t stride, const float* w, const float* bias,
                           int32_t C, const float* gamma, const float* beta, float eps, int32_t gelu, float* y,

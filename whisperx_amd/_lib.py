@@ -851,7 +851,8 @@ def channel_norm(x: torch.Tensor, gamma, beta, eps: float, gelu: bool, out: Opti
 def conv0_channel_norm(x: torch.Tensor, w: torch.Tensor, bias, stride: int, gamma, beta, eps: float, gelu: bool,
                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """wx_conv0_channel_norm: the 1-channel conv (w [C, 1, K] or [C, K]) over the samples x [S]
-    (contiguous fp32 device tensor), GroupNorm per channel, GELU; returns [Lout, C] time-major."""
+    (contiguous fp32 device tensor), GroupNorm per channel, GELU; returns [Lout, C] time-major.
+    (`bias` cancels in the per-channel normalisation: the kernels do not read it.)"""
     lib = load()
     S = int(x.shape[-1])
     C, K = int(w.shape[0]), int(w.shape[-1])

@@ -98,14 +98,17 @@ __global__ __launch_bounds__(256) void chan_apply_kernel(const float* __restrict
 // gelu(v * a[c] + b[c]) once.  A thread owns one channel (its k weights in registers) over
 // kC0Rows consecutive rows; a wave covers 64 consecutive channels, so every row's store is 256
 // contiguous bytes and the k waveform samples of a row are the same for the whole wave.
+// The conv bias is not read: GroupNorm with one group per channel subtracts the channel's mean, so a
+// per-channel constant cancels exactly, and a convolution summed onto a bias some tens of times the
+// signal's spread lost the digits the normalisation then magnifies (tests/test_gpu_conv_probes.py:
+// test_conv0_channel_norm_silence, 2.7e-5 against fp64 where fp32 torch is within 4.5e-6).
 constexpr int kC0Rows = 16;  // rows per thread
 constexpr int kC0MaxK = 16;  // taps held in registers
 
 template <int K>
-__device__ __forceinline__ float conv0_at(const float* __restrict__ x, int64_t t, int stride, const float (&w)[K],
-                                          float bias) {
+__device__ __forceinline__ float conv0_at(const float* __restrict__ x, int64_t t, int stride, const float (&w)[K]) {
     const float* xr = x + t * stride;
-    float v = bias;
+    float v = 0.f;
 #pragma unroll
     for (int j = 0; j < K; ++j) v = v + xr[j] * w[j];  // (-ffp-contract=off: separate multiply and add)
     return v;
@@ -113,20 +116,19 @@ __device__ __forceinline__ float conv0_at(const float* __restrict__ x, int64_t t
 
 template <int K>
 __global__ __launch_bounds__(256) void conv0_stats_kernel(const float* __restrict__ x, int64_t L, int stride,
-                                                          const float* __restrict__ wt, const float* __restrict__ bias,
-                                                          int C, double* __restrict__ part /* [nblk][2][C] */) {
+                                                          const float* __restrict__ wt, int C,
+                                                          double* __restrict__ part /* [nblk][2][C] */) {
     const int c = blockIdx.x * kCols + (threadIdx.x & (kCols - 1));
     const int wv = threadIdx.x / kCols;
     float w[K];
 #pragma unroll
     for (int j = 0; j < K; ++j) w[j] = c < C ? wt[(int64_t)c * K + j] : 0.f;
-    const float b = (bias && c < C) ? bias[c] : 0.f;
     const int64_t t0 = ((int64_t)blockIdx.y * kRows + wv) * kC0Rows;
     double s = 0.0, q = 0.0;
     for (int r = 0; r < kC0Rows; ++r) {
         const int64_t t = t0 + r;
         if (t >= L) break;
-        const double v = (double)conv0_at<K>(x, t, stride, w, b);
+        const double v = (double)conv0_at<K>(x, t, stride, w);
         s += v;
         q += v * v;
     }
@@ -194,8 +196,8 @@ __device__ __forceinline__ float gelu_erf0(float v) { return 0.5f * v * (1.0f + 
 
 template <int K>
 __global__ __launch_bounds__(256) void conv0_apply_kernel(const float* __restrict__ x, int64_t L, int stride,
-                                                          const float* __restrict__ wt, const float* __restrict__ bias,
-                                                          int C, const float* __restrict__ ab, int gelu,
+                                                          const float* __restrict__ wt, int C,
+                                                          const float* __restrict__ ab, int gelu,
                                                           float* __restrict__ y) {
     const int c = blockIdx.x * kCols + (threadIdx.x & (kCols - 1));
     const int wv = threadIdx.x / kCols;
@@ -203,14 +205,13 @@ __global__ __launch_bounds__(256) void conv0_apply_kernel(const float* __restric
     float w[K];
 #pragma unroll
     for (int j = 0; j < K; ++j) w[j] = wt[(int64_t)c * K + j];
-    const float b = bias ? bias[c] : 0.f;
     const float sa = ab[c], sb = ab[C + c];
     const int64_t t0 = ((int64_t)blockIdx.y * kRows + wv) * kC0Rows;
 #pragma unroll 4
     for (int r = 0; r < kC0Rows; ++r) {
         const int64_t t = t0 + r;
         if (t >= L) break;
-        float v = conv0_at<K>(x, t, stride, w, b) * sa + sb;
+        float v = conv0_at<K>(x, t, stride, w) * sa + sb;
         if (gelu) v = gelu_erf0(v);
         y[t * C + c] = v;
     }
@@ -225,9 +226,9 @@ __global__ __launch_bounds__(256) void conv0_apply_kernel(const float* __restric
 constexpr int kC0R = 32;  // rows per wave
 
 template <int K, int S>
-__device__ __forceinline__ float conv0_row(const float (&sv)[((kC0R - 1) * S + K + 63) / 64], int r, const float (&w)[K],
-                                           float b) {
-    float acc = b;
+__device__ __forceinline__ float conv0_row(const float (&sv)[((kC0R - 1) * S + K + 63) / 64], int r,
+                                           const float (&w)[K]) {
+    float acc = 0.f;
 #pragma unroll
     for (int j = 0; j < K; ++j) {
         const int k = r * S + j;
@@ -254,8 +255,8 @@ __device__ __forceinline__ void conv0_samples(const float* __restrict__ x, int64
 // form, conv0_samples + conv0_row, stays for the last wave).  Same fma chain per row.
 template <int K, int S>
 __device__ __forceinline__ float conv0_row_s(const float* __restrict__ xs /* wave-uniform */, int r,
-                                             const float (&w)[K], float b) {
-    float acc = b;
+                                             const float (&w)[K]) {
+    float acc = 0.f;
 #pragma unroll
     for (int j = 0; j < K; ++j) acc = fmaf(xs[r * S + j], w[j], acc);
     return acc;
@@ -263,8 +264,7 @@ __device__ __forceinline__ float conv0_row_s(const float* __restrict__ xs /* wav
 
 template <int K, int S>
 __global__ __launch_bounds__(256) void conv0_stats_rl_kernel(const float* __restrict__ x, int64_t nsamp, int64_t L,
-                                                             const float* __restrict__ wt,
-                                                             const float* __restrict__ bias, int C,
+                                                             const float* __restrict__ wt, int C,
                                                              double* __restrict__ part /* [nblk][2][C] */) {
     const int lc = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int c = blockIdx.x * 64 + lc;
@@ -272,7 +272,6 @@ __global__ __launch_bounds__(256) void conv0_stats_rl_kernel(const float* __rest
     float w[K];
 #pragma unroll
     for (int j = 0; j < K; ++j) w[j] = wt[(int64_t)cc * K + j];
-    const float b = bias ? bias[cc] : 0.f;
     const int64_t t0 = ((int64_t)blockIdx.y * 4 + wv) * kC0R;
     const int64_t nr = L - t0;
     double sm = 0.0, q = 0.0;
@@ -280,7 +279,7 @@ __global__ __launch_bounds__(256) void conv0_stats_rl_kernel(const float* __rest
         const float* xs = x + t0 * S;
 #pragma unroll
         for (int r = 0; r < kC0R; ++r) {
-            const double d = (double)conv0_row_s<K, S>(xs, r, w, b);
+            const double d = (double)conv0_row_s<K, S>(xs, r, w);
             if (r < nr) {
                 sm += d;
                 q = fma(d, d, q);
@@ -291,7 +290,7 @@ __global__ __launch_bounds__(256) void conv0_stats_rl_kernel(const float* __rest
         conv0_samples<K, S>(x, nsamp, t0, sv);
 #pragma unroll
         for (int r = 0; r < kC0R; ++r) {
-            const double d = (double)conv0_row<K, S>(sv, r, w, b);
+            const double d = (double)conv0_row<K, S>(sv, r, w);
             if (r < nr) {
                 sm += d;
                 q = fma(d, d, q);
@@ -312,8 +311,7 @@ __global__ __launch_bounds__(256) void conv0_stats_rl_kernel(const float* __rest
 
 template <int K, int S>
 __global__ __launch_bounds__(256) void conv0_apply_rl_kernel(const float* __restrict__ x, int64_t nsamp, int64_t L,
-                                                             const float* __restrict__ wt,
-                                                             const float* __restrict__ bias, int C,
+                                                             const float* __restrict__ wt, int C,
                                                              const float* __restrict__ ab, int gelu,
                                                              float* __restrict__ y) {
     const int lc = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
@@ -322,7 +320,6 @@ __global__ __launch_bounds__(256) void conv0_apply_rl_kernel(const float* __rest
     float w[K];
 #pragma unroll
     for (int j = 0; j < K; ++j) w[j] = wt[(int64_t)cc * K + j];
-    const float b = bias ? bias[cc] : 0.f;
     const float sa = ab[cc], sb = ab[C + cc];
     const int64_t t0 = ((int64_t)blockIdx.y * 4 + wv) * kC0R;
     const int64_t nr = L - t0;
@@ -331,7 +328,7 @@ __global__ __launch_bounds__(256) void conv0_apply_rl_kernel(const float* __rest
         const float* xs = x + t0 * S;
 #pragma unroll
         for (int r = 0; r < kC0R; ++r) {
-            float v = conv0_row_s<K, S>(xs, r, w, b) * sa + sb;
+            float v = conv0_row_s<K, S>(xs, r, w) * sa + sb;
             if (gelu) v = gelu_erf0(v);
             if (r < nr && c < C) yr[(int64_t)r * C] = v;
         }
@@ -340,7 +337,7 @@ __global__ __launch_bounds__(256) void conv0_apply_rl_kernel(const float* __rest
         conv0_samples<K, S>(x, nsamp, t0, sv);
 #pragma unroll
         for (int r = 0; r < kC0R; ++r) {
-            float v = conv0_row<K, S>(sv, r, w, b) * sa + sb;
+            float v = conv0_row<K, S>(sv, r, w) * sa + sb;
             if (gelu) v = gelu_erf0(v);
             if (r < nr && c < C) yr[(int64_t)r * C] = v;
         }
@@ -668,6 +665,8 @@ __global__ __launch_bounds__(256) void add_ln_kernel(const float* __restrict__ a
 // summation order differs); bias, erf GELU and optionally the residual (h + pos) fused.
 constexpr int kPcFrames = 128;  // output frames per block (4 waves x 32)
 constexpr int kPcK = 128;       // taps (wav2vec2's num_conv_pos_embeddings)
+constexpr int kPcBlock = 4;     // taps per summation block (a power of two that divides kPcK)
+static_assert(kPcK % kPcBlock == 0 && (kPcBlock & (kPcBlock - 1)) == 0, "posconv: whole blocks of taps");
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct PosConvArgs {
@@ -737,14 +736,18 @@ __global__ __launch_bounds__(256) void posconv_kernel(PosConvArgs a) {
     bstore(0);
     __syncthreads();
     const int l = threadIdx.x & 63, wv = threadIdx.x >> 6, q = l >> 4, r16 = l & 15;
-    f32x4 acc[2][NOB];
+    // Blocked summation: kPcBlock taps (kPcBlock Cg products) are summed in `part` and then added to
+    // the total.  One chain over all K Cg = 6,144 / 8,192 products was 6 to 9 times less accurate than
+    // torch's fp32 conv (tests/test_gpu_conv_probes.py: test_posconv_against_fp64); the error now grows
+    // with the block length and the block count instead of with their product.
+    f32x4 acc[2][NOB], part[2][NOB];
 #pragma unroll
     for (int fb = 0; fb < 2; ++fb)
 #pragma unroll
-        for (int ob = 0; ob < NOB; ++ob) acc[fb][ob] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int ob = 0; ob < NOB; ++ob) acc[fb][ob] = part[fb][ob] = f32x4{0.f, 0.f, 0.f, 0.f};
     // A fragment rows: frame wv 32 + 16 fb + r16 of the tile, shifted by the tap
     const float* xrow = xa + (wv * 32 + r16) * RS + 4 * q;
-    for (int j = 0; j < kPcK; ++j) {
+    auto tap = [&](int j) {
         if (j + 1 < kPcK) bload(j + 1);
         __builtin_amdgcn_sched_barrier(0);
         const float* bb = wb[j & 1] + (q * CG + r16) * 4;
@@ -759,14 +762,27 @@ __global__ __launch_bounds__(256) void posconv_kernel(PosConvArgs a) {
             for (int fb = 0; fb < 2; ++fb)
 #pragma unroll
                 for (int ob = 0; ob < NOB; ++ob) {
-                    acc[fb][ob] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[fb].x, bv[ob].x, acc[fb][ob], 0, 0, 0);
-                    acc[fb][ob] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[fb].y, bv[ob].y, acc[fb][ob], 0, 0, 0);
-                    acc[fb][ob] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[fb].z, bv[ob].z, acc[fb][ob], 0, 0, 0);
-                    acc[fb][ob] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[fb].w, bv[ob].w, acc[fb][ob], 0, 0, 0);
+                    part[fb][ob] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[fb].x, bv[ob].x, part[fb][ob], 0, 0, 0);
+                    part[fb][ob] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[fb].y, bv[ob].y, part[fb][ob], 0, 0, 0);
+                    part[fb][ob] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[fb].z, bv[ob].z, part[fb][ob], 0, 0, 0);
+                    part[fb][ob] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[fb].w, bv[ob].w, part[fb][ob], 0, 0, 0);
                 }
         }
         if (j + 1 < kPcK) bstore((j + 1) & 1);
         __syncthreads();
+    };
+    // (the tap loop unrolled by the block: with the block's end behind a branch in the rolled loop the
+    // Cg = 48 instance was 10% slower than the single chain, this way it is 4% faster)
+    for (int jb = 0; jb < kPcK; jb += kPcBlock) {
+#pragma unroll
+        for (int jj = 0; jj < kPcBlock; ++jj) tap(jb + jj);
+#pragma unroll
+        for (int fb = 0; fb < 2; ++fb)
+#pragma unroll
+            for (int ob = 0; ob < NOB; ++ob) {
+                acc[fb][ob] += part[fb][ob];
+                part[fb][ob] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
     }
     // accumulator (fb, ob) register v: frame 16 fb + 4 q + v of the wave's 32, output 16 ob + r16
 #pragma unroll
@@ -823,6 +839,7 @@ extern "C" int wx_conv0_channel_norm(const float* x, int64_t S, int32_t K, int32
                                      int32_t gelu, float* y, void* workspace, size_t workspace_bytes, void* stream) {
     using namespace wxe;
     if (S < 0 || C <= 0 || K < 1 || K > kC0MaxK || stride < 1 || !x || !w || !y) return WX_E_INVALID;
+    (void)bias;  // cancels in the per-channel normalisation (see above): never added
     const int64_t L = S >= K ? (S - K) / stride + 1 : 0;
     if (L == 0) return WX_OK;
     if (!workspace || workspace_bytes < wx_conv0_channel_norm_workspace_bytes(L, C)) return WX_E_WORKSPACE;
@@ -835,19 +852,19 @@ extern "C" int wx_conv0_channel_norm(const float* x, int64_t S, int32_t K, int32
     float* ab = reinterpret_cast<float*>(part + (size_t)nblk * 2 * C);
     if (rl) {
         const dim3 grid((C + 63) / 64, (unsigned)nblk);
-        hipLaunchKernelGGL((conv0_stats_rl_kernel<10, 5>), grid, dim3(256), 0, st, x, S, L, w, bias, C, part);
+        hipLaunchKernelGGL((conv0_stats_rl_kernel<10, 5>), grid, dim3(256), 0, st, x, S, L, w, C, part);
         hipLaunchKernelGGL(conv0_finish_kernel, dim3((C + kCols - 1) / kCols), dim3(kCols * kRows), 0, st, part,
                            (int)nblk, L, C, gamma, beta, eps, ab);
-        hipLaunchKernelGGL((conv0_apply_rl_kernel<10, 5>), grid, dim3(256), 0, st, x, S, L, w, bias, C, ab, gelu, y);
+        hipLaunchKernelGGL((conv0_apply_rl_kernel<10, 5>), grid, dim3(256), 0, st, x, S, L, w, C, ab, gelu, y);
         return wx::launch_status();
     }
     const dim3 grid((C + kCols - 1) / kCols, (unsigned)nblk), blk(kCols * kRows);
 #define WX_C0(KK)                                                                                              \
     case KK:                                                                                                   \
-        hipLaunchKernelGGL(conv0_stats_kernel<KK>, grid, blk, 0, st, x, L, stride, w, bias, C, part);           \
+        hipLaunchKernelGGL(conv0_stats_kernel<KK>, grid, blk, 0, st, x, L, stride, w, C, part);           \
         hipLaunchKernelGGL(conv0_finish_kernel, dim3((C + kCols - 1) / kCols), blk, 0, st, part, (int)nblk, L, C, \
                            gamma, beta, eps, ab);                                                              \
-        hipLaunchKernelGGL(conv0_apply_kernel<KK>, grid, blk, 0, st, x, L, stride, w, bias, C, ab, gelu, y);    \
+        hipLaunchKernelGGL(conv0_apply_kernel<KK>, grid, blk, 0, st, x, L, stride, w, C, ab, gelu, y);    \
         break;
     switch (K) {
         WX_C0(1) WX_C0(2) WX_C0(3) WX_C0(4) WX_C0(5) WX_C0(6) WX_C0(7) WX_C0(8) WX_C0(9) WX_C0(10) WX_C0(11)

@@ -164,8 +164,8 @@ __global__ __launch_bounds__(kThreads) void sinc_stage_kernel(SincArgs a) {
 // [B L, 60] output read and written per tap (memory-bound, ~33 ms per hour of audio).  Here
 // one block per (window, 128 output frames): the 132 input rows sit in LDS once, the taps'
 // [Cin, 64] weight slabs stream through one LDS slab, 4 waves x 32 frames x 64
-// outputs (60 used) on v_mfma_f32_16x16x4_f32; + bias, written once.  fp32 (fma chains: not
-// bit-identical to the GEMM route, tests compare at fp32 tolerance).
+// outputs (60 used) on v_mfma_f32_16x16x4_f32, each tap summed on its own; + bias, written once.
+// fp32 (fma chains: not bit-identical to the GEMM route; within 4 x fp32 torch's error of fp64).
 constexpr int kCkFrames = 128;
 
 // One weight slab in LDS (round 6): a block is 64 KB (Cin 80), so two blocks share a CU and
@@ -173,11 +173,13 @@ constexpr int kCkFrames = 128;
 // — 84 KB, one block per CU, the next tap's store overlapped inside the block: 1 ms per hour
 // slower.)
 
+// amdgpu_waves_per_eu(3): the CINP = 64 instance's 52 KB of LDS let three blocks share a CU, which
+// needs at most 168 registers per lane; left alone, hipcc spread the two accumulator sets over
+// 210 (VGPRs + AGPRs) and the third block was lost (8% slower at Cin 60).
 template <int CINP, int KT>
-__global__ __launch_bounds__(256) void conv_taps_kernel(const float* __restrict__ x, int Cin, int L,
-                                                        const float* __restrict__ wp /* [KT][CINP/4][64][4] */,
-                                                        const float* __restrict__ bias, float* __restrict__ y,
-                                                        int Cout, int Lout) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void conv_taps_kernel(
+    const float* __restrict__ x, int Cin, int L, const float* __restrict__ wp /* [KT][CINP/4][64][4] */,
+    const float* __restrict__ bias, float* __restrict__ y, int Cout, int Lout) {
     typedef float f32x4 __attribute__((ext_vector_type(4)));
     constexpr int RS = CINP + 4;
     constexpr int WR = kCkFrames + KT - 1;
@@ -235,6 +237,14 @@ __global__ __launch_bounds__(256) void conv_taps_kernel(const float* __restrict_
         // after the barrier, a global round trip per tap)
         __builtin_amdgcn_sched_barrier(0);
         const float* bb = wb + (q * 64 + r16) * 4;
+        // one tap (CINP products) is summed on its own and then added to the total: a single chain
+        // over the KT CINP products was up to 7 times less accurate than torch's fp32 conv
+        // (tests/test_gpu_conv_probes.py: test_conv_taps_against_fp64)
+        f32x4 part[2][NOB];
+#pragma unroll
+        for (int fb = 0; fb < 2; ++fb)
+#pragma unroll
+            for (int ob = 0; ob < NOB; ++ob) part[fb][ob] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ic = 0; ic < NIC; ++ic) {
             float4 av[2], bv[NOB];
@@ -246,12 +256,16 @@ __global__ __launch_bounds__(256) void conv_taps_kernel(const float* __restrict_
             for (int fb = 0; fb < 2; ++fb)
 #pragma unroll
                 for (int ob = 0; ob < NOB; ++ob) {
-                    acc[fb][ob] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[fb].x, bv[ob].x, acc[fb][ob], 0, 0, 0);
-                    acc[fb][ob] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[fb].y, bv[ob].y, acc[fb][ob], 0, 0, 0);
-                    acc[fb][ob] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[fb].z, bv[ob].z, acc[fb][ob], 0, 0, 0);
-                    acc[fb][ob] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[fb].w, bv[ob].w, acc[fb][ob], 0, 0, 0);
+                    part[fb][ob] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[fb].x, bv[ob].x, part[fb][ob], 0, 0, 0);
+                    part[fb][ob] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[fb].y, bv[ob].y, part[fb][ob], 0, 0, 0);
+                    part[fb][ob] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[fb].z, bv[ob].z, part[fb][ob], 0, 0, 0);
+                    part[fb][ob] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[fb].w, bv[ob].w, part[fb][ob], 0, 0, 0);
                 }
         }
+#pragma unroll
+        for (int fb = 0; fb < 2; ++fb)
+#pragma unroll
+            for (int ob = 0; ob < NOB; ++ob) acc[fb][ob] += part[fb][ob];
         __syncthreads();  // every wave is done with tap j's slab
         if (j + 1 < KT) {
             bstore();
