@@ -61,6 +61,73 @@ def test_vad_aggregate_kernel_vs_oracle():
         assert np.array_equal(got, exp, equal_nan=True), (n_chunks, K, C)
 
 
+def _exact_aggregate(sc, starts, n_frames, missing):
+    """Frame by frame from the definition, for scores that are multiples of 2**-8: a frame's sum is
+    then exact in fp32 in any order, and the value is fp32(sum) / fp32(count)."""
+    K = sc.shape[1]
+    m = sc.astype(np.float64).max(axis=-1)  # (np.max: a NaN class makes the window frame NaN)
+    out = np.full(n_frames, missing, np.float32)
+    for f in range(n_frames):
+        vals = [m[c, f - s] for c, s in enumerate(starts) if 0 <= f - s < K and not np.isnan(m[c, f - s])]
+        if vals:
+            total = float(np.sum(vals))
+            assert total * 256 == int(total * 256) and total < 2 ** 16
+            out[f] = np.float32(total) / np.float32(len(vals))
+    return out
+
+
+VAD_EXACT = [
+    # K, starts (non-decreasing): gaps wider than K (frames in the middle that no window covers), three
+    # windows on one start frame, a last window cut off by n_frames, windows at and past n_frames
+    (20, [0, 5, 5, 5, 40, 41, 100, 230, 245, 256, 257, 300]),
+    (1, [0, 0, 2, 2, 2, 7, 255, 256, 256, 257, 258]),
+    (293, [0, 0, 0, 1, 200, 256, 256]),
+]
+VAD_EXACT_FRAMES, VAD_EXACT_MISSING = 257, -1.0  # (a second block of one frame)
+
+
+def _vad_exact_case(K, starts):
+    """Scores (multiples of 2**-8, 3 classes) and the expected frames.  A NaN class masks its own
+    window frame and nothing else: one under three windows, one under two, and one in the last frame
+    of window 6, which at K 20 and K 1 is the only window on that frame (the frame is then missing)."""
+    n_frames, missing = VAD_EXACT_FRAMES, VAD_EXACT_MISSING
+    rng = np.random.default_rng([K, len(starts)])
+    sc = (rng.integers(0, 257, (len(starts), K, 3)) / 256.0).astype(np.float32)
+    sc[1, 0, 1] = np.nan
+    sc[4, K // 2, 2] = np.nan
+    sc[6, K - 1, 0] = np.nan
+    exp = _exact_aggregate(sc, starts, n_frames, missing)
+    covered = np.zeros(n_frames, bool)
+    for s in starts:
+        covered[s:s + K] = True
+    assert covered[256] and (exp[~covered] == missing).all()
+    if K < 293:
+        assert not covered[1:-1].all()  # frames in the middle that no window covers
+        alone = starts[6] + K - 1
+        assert covered[alone] and exp[alone] == missing and exp[alone - 1 if K > 1 else 256] != missing
+    return sc, exp
+
+
+@pytest.mark.parametrize("K,starts", VAD_EXACT)
+def test_exact_aggregate_equals_the_oracle(K, starts):
+    sc, exp = _vad_exact_case(K, starts)
+    got = oracle.vad_aggregate(sc, starts, VAD_EXACT_FRAMES, missing=VAD_EXACT_MISSING)
+    assert np.array_equal(got.view(np.uint32), exp.view(np.uint32))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("K,starts", VAD_EXACT)
+def test_vad_aggregate_exact_probe(K, starts):
+    """wx_vad_aggregate on scores whose sums are exact in any order: bit-equal to the definition."""
+    from whisperx_amd import _lib
+
+    sc, exp = _vad_exact_case(K, starts)
+    got = _lib.vad_aggregate(torch.from_numpy(sc).cuda(), starts, VAD_EXACT_FRAMES, missing=VAD_EXACT_MISSING).cpu().numpy()
+    assert got.dtype == np.float32 and got.shape == (VAD_EXACT_FRAMES,)
+    bad = np.nonzero(got.view(np.uint32) != exp.view(np.uint32))[0]
+    assert bad.size == 0, (K, bad[:8], got[bad[:8]], exp[bad[:8]])
+
+
 @pytest.mark.gpu
 def test_vad_producer_end_to_end_device_scores():
     """60 s of audio through the producer; its scores equal the oracle aggregation of its own
