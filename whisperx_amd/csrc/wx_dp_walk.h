@@ -533,6 +533,9 @@ constexpr int kSpecMinBlocks = 4;  // blocks per segment at least
 constexpr int kSpecOverlap = 2;  // unrecorded blocks a walker starts above its segment (A/B: 1, 3, 4 slower)
 // wave 0's t_start search, in walk blocks (A/B: 1, 3 or 5 within noise)
 constexpr int kSpecArgmaxBlocks = 3;
+// columns a walker's guess lies above the straight line, times (T - 2 N) / T (simulated on the
+// decision bits, tools/walk_guess_sim.py: 0 leaves several times as many segment tops unmerged, 24 most of them)
+constexpr int kSpecBias = 8;
 template <class Src>
 __device__ __forceinline__ int walk_spec(Src& lw, int N, int T, const float* cn, unsigned* cmask, bool cmask_in_lds,
                                          int K, int* colrec, int* sbuf, int& t_start) {
@@ -597,9 +600,14 @@ __device__ __forceinline__ int walk_spec(Src& lw, int N, int T, const float* cn,
         top = sw.lo(wv - 1) - 1;
         const int lo = sw.lo(wv), sb = top + kSpecOverlap;
         // guess: the straight line from (0, 0) to (tref, N), inside the cells the path can
-        // occupy at time 32 (sb + 1) (column <= time, N - column <= remaining steps)
+        // occupy at time 32 (sb + 1) (column <= time, N - column <= remaining steps), moved up by
+        // kSpecBias (tref - 2 N) / tref columns: a walker d columns above the true path sheds its
+        // surplus on the frames that emit no token, ~d tref / (tref - N) frames, one d columns
+        // below it merges only d tokens further down, ~d tref / N frames, so while N < tref / 2
+        // an over-guess merges inside the overlap more often than an under-guess of the same
+        // size (simulated unmerged segment tops of config 2: 16 -> 0 of 1,792)
         const int tt = 32 * (sb + 1);
-        int g = (int)(((int64_t)N * tt + tref / 2) / tref);
+        int g = (int)(((int64_t)N * tt + tref / 2 + (int64_t)kSpecBias * (tref - 2 * N)) / tref);
         g = min(max(g, max(1, N - (tref - tt))), min(N, tt));
         for (int bb = lo + lane; bb <= top; bb += kWave) colrec[bb] = -1;
         go = true;
