@@ -33,6 +33,9 @@
  *   wx_decode_attention_f32 <- whisperx/asr.py:53-62, 245-257  generate_segment_batched and
  *                        detect_language (the text decoder's self- and cross-attention of one
  *                        decode step: one query row per sequence and head)
+ *   wx_decode_attention_f32_grouped, wx_beam_topk <- whisperx/asr.py:301-304  beam_size 5, the
+ *                        reference's default (G beams of a chunk on the chunk's one cross-attention
+ *                        K / V; the 2G best continuations of a chunk per step)
  *
  * Conventions
  *   - All data pointers are DEVICE pointers (allocated by the caller; the library never
@@ -476,6 +479,53 @@ int wx_decode_attention_f32(const float* q, const float* k, const float* v, floa
                             int32_t L, int32_t D, const int64_t* q_strides, const int64_t* k_strides,
                             const int64_t* v_strides, float scale, void* workspace, size_t workspace_bytes,
                             void* stream);
+
+/* The same attention for G queries per (batch, head) that share its keys and values: the G beams
+ * of one audio chunk in beam search, whose cross-attention K / V are the chunk's one [P][2 H 64]
+ * block (WhisperDecoder.beam_search; the reference's default is beam_size 5, asr.py:301-304),
+ *     o[b][g][h][:] = sum_{j<L} softmax_j(scale * q[b][g][h][:] . k[b][h][j][:]) v[b][h][j][:]
+ *   q: row (b, g, h) at q + b q_strides[0] + g q_strides[1] + h q_strides[2]; k, v, the stride and
+ *   alignment rules as above.  o: [B][G][H][64] contiguous.  1 <= G <= WX_DECODE_ATTENTION_MAX_GROUP.
+ *   workspace: wx_decode_attention_grouped_workspace_bytes(B, G, H, L) bytes.
+ * Same chunking, one workgroup per (chunk, head, batch): it loads every key and value row once and
+ * scores it against the G queries, so K / V are read once per chunk however many beams there are;
+ * the chunks are merged by the launch above's merge kernel over B G H rows.  The per-query
+ * arithmetic and every summation order are those of wx_decode_attention_f32: row (b, g, h) is
+ * bit-identical to what that entry point returns for the query on the same K / V, whatever B and
+ * G are and whatever the other queries of the group hold.  Rows j >= L are never read.
+ * B < 0, G outside 1..8, H < 1, L < 1, D != 64: WX_E_INVALID; then B == 0: WX_OK; then the checks
+ * above in the same order; all before anything is enqueued. */
+#define WX_DECODE_ATTENTION_MAX_GROUP 8
+size_t wx_decode_attention_grouped_workspace_bytes(int32_t B, int32_t G, int32_t H, int32_t L);
+int wx_decode_attention_f32_grouped(const float* q, const float* k, const float* v, float* o, int32_t B, int32_t G,
+                                    int32_t H, int32_t L, int32_t D, const int64_t* q_strides,
+                                    const int64_t* k_strides, const int64_t* v_strides, float scale, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+
+/* One beam-search selection step (WhisperDecoder.beam_search): B chunks of G beams, row r = b G + g
+ * of logits (V fp32 columns at logits + r row_stride; nothing at columns >= V is read) and cum[r],
+ * the beam's running sum of log-probabilities.
+ *     lse_r = m + log(sum_t exp(x[r][t] - m)), m = max_t x[r][t], in fp32, in a summation order
+ *             that depends on V alone (slices of WX_BEAM_TOPK_SLICE columns, each 4 x 1024: a
+ *             lane's 16 columns in order, a butterfly over the wave, the 4 waves in order, then
+ *             the slices 64 apart in order and a butterfly);
+ *     candidate (g, t) of chunk b scores cum[r] + (x[r][t] - lse_r).
+ * scores / index [B][2G]: the 2G best of the chunk's G V candidates, ordered by score descending,
+ * then lower g, then higher logit, then lower t; index = g V + t.  (A row's candidates are
+ * preselected by logit, then by lower t, before lse_r is known: within a row the score never
+ * decreases with the logit.)  A logit of -inf (a suppressed id) or a cum of -inf (a dead beam) is
+ * an ordinary input: such a candidate scores -inf, never NaN, and ranks after every finite one
+ * in the order above; fewer than 2G finite candidates is legal.  Chunk b's output is bit-identical
+ * whatever B is.  Two launches (a pass over the logits, one workgroup per slice and row; a merge,
+ * one workgroup per chunk), no atomics.
+ *   workspace: wx_beam_topk_workspace_bytes(B, G, V) bytes (16-byte aligned).
+ * B < 0, G outside 1..8, V < 2G or V > 2^24, row_stride < V: WX_E_INVALID; then B == 0: WX_OK; a
+ * null pointer, a misaligned workspace, B G above 65535 (a grid dimension): WX_E_INVALID; a
+ * short workspace: WX_E_WORKSPACE; all before anything is enqueued. */
+#define WX_BEAM_TOPK_SLICE 4096
+size_t wx_beam_topk_workspace_bytes(int32_t B, int32_t G, int32_t V);
+int wx_beam_topk(const float* logits, int64_t row_stride, const float* cum, int32_t B, int32_t G, int32_t V,
+                 float* scores, int32_t* index, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -20,6 +20,16 @@ positions, 1500 encoder positions:
     device (its per-step figure is that loop's time over its 64 steps; it takes the prompt in one
     forward, ours in three steps).  Both loops check for completion, and so synchronise, every step.
 
+(c) --arms beam (its own record, profiles/whisper_beam_<host>.json): beam search at --beams 5.
+    The grouped cross-attention launch (wx_decode_attention_f32_grouped: B chunks, G queries each on
+    the chunk's one K / V) at G in {1, 5, 8} against the ungrouped launch at B rows and at B G rows on
+    K / V replicated G times, L = 1500, B = 16, by (a)'s ring method; wx_beam_topk against torch's
+    log_softmax + add + topk on [16 G, 51865] logits; and `beam_search` of 64 tokens for 16 chunks
+    against the route without the two kernels: B G rows through the same step machinery with the
+    cross-attention tensors replicated by repeat_interleave, the ungrouped kernel and torch's
+    selection (the same host walk and cache reorder).  Where the replicated tensors do not fit, the
+    baseline's chunk count is halved until they do, and the record says what it was.
+
 Prints one JSON line; --out writes it to a file (profiles/whisper_decoder_<host>.json).
 """
 from __future__ import annotations
@@ -82,8 +92,181 @@ def attention_rows(D, args, torch, F, _lib, dev):
     return rows
 
 
+def grouped_attention_rows(D, args, torch, _lib, dev, B=CHUNKS, L=P):
+    """(c): one cross-attention launch for B chunks of G beams, grouped on [B, L, 2D] against
+    ungrouped on B rows (one beam's work) and on B G rows of a [B G, L, 2D] replica."""
+    H = D // 64
+
+    def halves(t):
+        return tuple(t[:, :, j * D:(j + 1) * D].view(t.shape[0], L, H, 64).transpose(1, 2) for j in range(2))
+
+    rows = []
+    for G in (1, 5, 8):
+        nbytes = 2 * B * H * L * 64 * 4
+        ring = max(2, min(32, -(-args.ring_bytes // (nbytes * G))))
+        q = torch.randn((B, G, H, 64), device=dev)
+        shared = [torch.randn((B, L, 2 * D), device=dev) for _ in range(ring)]
+        out = torch.empty((B, G, H, 64), device=dev)
+        out1 = torch.empty((B, H, 64), device=dev)
+        q1 = q[:, 0].contiguous()
+        qr = q.view(B * G, H, 64)
+
+        def grouped(i):
+            k, v = halves(shared[i % ring])
+            return _lib.decode_attention_f32_grouped(q, k, v, 0.125, out=out)
+
+        def ungrouped_b(i):
+            k, v = halves(shared[i % ring])
+            return _lib.decode_attention_f32(q1, k, v, 0.125, out=out1)
+
+        with torch.inference_mode():
+            r = {"L": L, "B": B, "G": G, "H": H, "kv_bytes_shared": nbytes, "kv_bytes_replicated": nbytes * G,
+                 "ring_buffers": ring,
+                 "grouped": event_timed(grouped, args.repeat, args.warmup, args.steps, torch),
+                 "ungrouped_B_rows": event_timed(ungrouped_b, args.repeat, args.warmup, args.steps, torch)}
+            want = grouped(0).clone()
+        del shared
+        torch.cuda.empty_cache()
+        replicated = [torch.randn((B * G, L, 2 * D), device=dev) for _ in range(ring)]
+        outr = torch.empty((B * G, H, 64), device=dev)
+
+        def ungrouped_bg(i):
+            k, v = halves(replicated[i % ring])
+            return _lib.decode_attention_f32(qr, k, v, 0.125, out=outr)
+
+        with torch.inference_mode():
+            r["ungrouped_BG_rows_replicated"] = event_timed(ungrouped_bg, args.repeat, args.warmup, args.steps, torch)
+        r["grouped"]["kv_bytes_per_s"] = nbytes / r["grouped"]["median_s"]
+        r["grouped"]["share_of_hbm_peak"] = r["grouped"]["kv_bytes_per_s"] / HBM_PEAK_BYTES_PER_S
+        r["grouped_vs_ungrouped_BG_rows"] = beats(r["grouped"], r["ungrouped_BG_rows_replicated"])
+        r["grouped_vs_ungrouped_B_rows"] = beats(r["grouped"], r["ungrouped_B_rows"])
+        r["output_finite"] = bool(torch.isfinite(want).all())
+        rows.append(r)
+        del replicated
+        torch.cuda.empty_cache()
+    return rows
+
+
+def torch_select(lg, cum, G):
+    """The selection without wx_beam_topk: log_softmax, add, topk over the chunk's G V candidates."""
+    import torch
+
+    R, Vv = lg.shape
+    sc = (torch.log_softmax(lg, -1) + cum[:, None]).view(R // G, G * Vv)
+    top = sc.topk(2 * G, dim=1)
+    return top.values, top.indices.to(torch.int32)
+
+
+def baseline_beam_search(dec, enc, prompt, eot, G, n_tokens, torch):
+    """beam_search's loop on what the decoder had before the grouped kernels: B G rows of a plain
+    state over the encoder states replicated G times (so is every cross-attention tensor), the
+    ungrouped attention kernel, torch_select, and the same host walk and cache reorder."""
+    with torch.inference_mode():
+        st = dec.start(enc.repeat_interleave(G, 0))
+        R, B = st.B, st.B // G
+        for t in prompt:
+            lg = dec._step(st, torch.full((R,), t, dtype=torch.int64, device=dec.device))
+        sums = [[0.0] + [float("-inf")] * (G - 1) for _ in range(B)]
+        ids = [[[] for _ in range(G)] for _ in range(B)]
+        identity = list(range(R))
+        for step in range(n_tokens):
+            lg[:, eot] = float("-inf")
+            cum = torch.tensor([x for row in sums for x in row], dtype=torch.float32).to(dec.device)
+            sc, idx = torch_select(lg, cum, G)
+            both = torch.cat([sc, idx.view(torch.float32)], 1).cpu()
+            sc, idx = both[:, :2 * G].tolist(), both[:, 2 * G:].contiguous().view(torch.int32).tolist()
+            parents, feed = list(identity), [eot] * R
+            for b in range(B):
+                live = [(*divmod(i, dec.V), s) for s, i in zip(sc[b], idx[b])][:G]  # (eot is suppressed: all live)
+                ids[b] = [ids[b][g] + [t] for g, t, _ in live]
+                sums[b] = [s for _, _, s in live]
+                for j, (g, t, _) in enumerate(live):
+                    parents[b * G + j], feed[b * G + j] = b * G + g, t
+            if step + 1 == n_tokens:
+                break
+            if parents != identity:
+                dec.reorder(st, torch.tensor(parents, dtype=torch.int64))
+            lg = dec._step(st, torch.tensor(feed, dtype=torch.int64).to(dec.device))
+    return [ids[b][0] for b in range(B)]
+
+
+def beam_arm(name, g, args, torch, _lib, dev):
+    from transformers import WhisperConfig, WhisperForConditionalGeneration
+
+    from whisperx_amd import WhisperDecoder
+
+    D, G = g["D"], args.beams
+    sync = torch.cuda.synchronize
+    eot = V - 1
+    r = {"shape": {**g, "heads": D // 64, "vocab": V, "max_target_positions": T, "encoder_positions": P}, "beams": G}
+    r["grouped_attention"] = grouped_attention_rows(D, args, torch, _lib, dev)
+    print(f"{name}: grouped attention timed", file=sys.stderr, flush=True)
+    lg = 4.0 * torch.randn((CHUNKS * G, V), device=dev)
+    cum = -torch.rand(CHUNKS * G, device=dev)
+    with torch.inference_mode():
+        a, b = _lib.beam_topk(lg, cum, G), torch_select(lg, cum, G)
+        r["topk"] = {"rows": CHUNKS * G, "G": G, "vocab": V,
+                     "index_equal_torch": float((a[1] == b[1]).float().mean()),
+                     "max_abs_score_diff_vs_torch": float((a[0] - b[0]).abs().max()),
+                     "ours": event_timed(lambda i: _lib.beam_topk(lg, cum, G), args.repeat, args.warmup, args.steps, torch),
+                     "torch": event_timed(lambda i: torch_select(lg, cum, G), args.repeat, args.warmup, args.steps, torch)}
+    r["topk"]["ours_vs_torch"] = beats(r["topk"]["ours"], r["topk"]["torch"])
+    cfg = WhisperConfig(d_model=D, encoder_layers=1, encoder_attention_heads=1, encoder_ffn_dim=64, num_mel_bins=80,
+                        max_source_positions=P, decoder_layers=g["layers"], decoder_attention_heads=D // 64,
+                        decoder_ffn_dim=4 * D, vocab_size=V, max_target_positions=T, pad_token_id=0, bos_token_id=1,
+                        eos_token_id=2, decoder_start_token_id=1)
+    hf = WhisperForConditionalGeneration(cfg).eval().model.decoder.to(dev)
+    dec = WhisperDecoder(hf, device=dev)
+    del hf
+    enc = torch.randn((CHUNKS, P, D), device=dev)
+
+    def ours():
+        return dec.beam_search(enc, PROMPT, eot, beam_size=G, max_length=len(PROMPT) + N_TOKENS, suppress_tokens=[eot])
+
+    def greedy():
+        return dec.generate(enc, PROMPT, eot, max_length=len(PROMPT) + N_TOKENS, suppress_tokens=[eot])
+
+    print(f"{name}: decoder built", file=sys.stderr, flush=True)
+    got = ours()
+    bs = {"chunks": CHUNKS, "beams": G, "generated_tokens": len(got[0][0].ids),
+          "beam_search": timed(ours, args.repeat, args.warmup, sync),
+          "greedy_generate": timed(greedy, args.repeat, args.warmup, sync)}
+    bs["beam_search_per_step"] = {k: v / N_TOKENS for k, v in bs["beam_search"].items() if k.endswith("_s")}
+    torch.cuda.empty_cache()
+    print(f"{name}: beam_search timed", file=sys.stderr, flush=True)
+    Bb = CHUNKS
+    while True:  # the replicated cross tensors: layers x Bb G x P x 2D x 4 bytes
+        try:
+            want = baseline_beam_search(dec, enc[:Bb], PROMPT, eot, G, N_TOKENS, torch)
+            bs["baseline"] = timed(lambda: baseline_beam_search(dec, enc[:Bb], PROMPT, eot, G, N_TOKENS, torch),
+                                   args.repeat, args.warmup, sync)
+            break
+        except torch.cuda.OutOfMemoryError:
+            torch.cuda.empty_cache()
+            if Bb == 1:
+                bs["baseline"] = "not measured (the replicated tensors of one chunk do not fit)"
+                break
+            Bb //= 2
+    bs["baseline_chunks"] = Bb
+    bs["baseline_replicated_cross_bytes"] = g["layers"] * Bb * G * P * 2 * D * 4
+    bs["shared_cross_bytes"] = g["layers"] * CHUNKS * P * 2 * D * 4
+    if isinstance(bs["baseline"], dict):
+        bs["best_ids_equal_baseline"] = sum(h[0].ids == w for h, w in zip(got, want)) / Bb
+        if Bb == CHUNKS:
+            bs["beam_search_vs_baseline"] = beats(bs["beam_search"], bs["baseline"])
+        else:  # per chunk: the baseline ran fewer
+            bs["baseline_s_per_chunk"] = bs["baseline"]["median_s"] / Bb
+            bs["beam_search_s_per_chunk"] = bs["beam_search"]["median_s"] / CHUNKS
+    r["beam_search"] = bs
+    del dec, enc
+    torch.cuda.empty_cache()
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--arms", default="decoder", choices=["decoder", "beam"], help="(a) and (b), or (c)")
+    ap.add_argument("--beams", type=int, default=5)
     ap.add_argument("--geometries", default="base,large-v2")
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
@@ -108,6 +291,10 @@ def main():
     eot = V - 1  # suppressed: both greedy loops run their full length
     for name in args.geometries.split(","):
         g = GEOMETRIES[name]
+        if args.arms == "beam":
+            torch.manual_seed(args.seed)
+            result["geometries"][name] = beam_arm(name, g, args, torch, _lib, dev)
+            continue
         D = g["D"]
         torch.manual_seed(args.seed)
         r = {"shape": {**g, "heads": D // 64, "vocab": V, "max_target_positions": T, "encoder_positions": P}}

@@ -25,7 +25,7 @@ SRC_PATH = os.path.join(_HERE, "csrc", "wx_align.hip")
 SRC_PATHS = [SRC_PATH, os.path.join(_HERE, "csrc", "wx_binarize.hip"), os.path.join(_HERE, "csrc", "wx_emission.hip"),
              os.path.join(_HERE, "csrc", "wx_vad.hip"), os.path.join(_HERE, "csrc", "wx_diarize.hip"),
              os.path.join(_HERE, "csrc", "wx_mel.hip"), os.path.join(_HERE, "csrc", "wx_whisper.hip"),
-             os.path.join(_HERE, "csrc", "wx_decode.hip")]
+             os.path.join(_HERE, "csrc", "wx_decode.hip"), os.path.join(_HERE, "csrc", "wx_beam.hip")]
 INST_PATH = os.path.join(_HERE, "csrc", "wx_align_inst.hip")
 HDR_PATHS = sorted(glob.glob(os.path.join(_HERE, "csrc", "*.h"))) + [INST_PATH]  # (a new header: a rebuild)
 INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
@@ -108,6 +108,11 @@ SIGNATURES = {
     "wx_whisper_stem": (ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _sz, _vp]),
     "wx_decode_attention_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "wx_decode_attention_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _vp, _sz, _vp]),
+    "wx_decode_attention_grouped_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "wx_decode_attention_f32_grouped": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32,
+                                                       _vp, _sz, _vp]),
+    "wx_beam_topk_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "wx_beam_topk": (ctypes.c_int, [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
 }
 
 
@@ -763,6 +768,76 @@ def decode_attention_f32(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scal
         _check(lib.wx_decode_attention_f32(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, H, L, D, st[0], st[1], st[2],
                                            float(scale), _ptr(ws), ws.numel(), ctypes.c_void_p(stream.cuda_stream)))
     return out
+
+
+DECODE_MAX_GROUP = 8  # WX_DECODE_ATTENTION_MAX_GROUP: queries per (batch, head) of the grouped kernel
+BEAM_TOPK_SLICE = 4096  # WX_BEAM_TOPK_SLICE: columns per workgroup of wx_beam_topk's first pass
+
+
+def decode_attention_f32_grouped(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float,
+                                 L: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """wx_decode_attention_f32_grouped: G query rows per (batch, head), q [B, G, H, 64] (the beams of
+    one chunk), against rows 0 .. L - 1 of the k / v [B, H, Lcap, 64] they share, read in place
+    under decode_attention_f32's stride and alignment rules.  Returns [B, G, H, 64] contiguous
+    (`out` when given) on the current stream; row (b, g, h) has the bits decode_attention_f32
+    gives that query on the same k / v."""
+    lib = load()
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise WXError(f"decode_attention_f32_grouped: q {tuple(q.shape)} / k {tuple(k.shape)} / v {tuple(v.shape)} "
+                      "are not [B, G, H, 64] / [B, H, Lcap, 64] / [B, H, Lcap, 64]")
+    B, G, H, D = (int(x) for x in q.shape)
+    Lcap = int(k.shape[2])
+    L = Lcap if L is None else int(L)
+    if tuple(k.shape) != (B, H, Lcap, D) or tuple(v.shape) != (B, H, Lcap, D) or not 1 <= L <= Lcap:
+        raise WXError(f"decode_attention_f32_grouped: k {tuple(k.shape)} / v {tuple(v.shape)} do not hold {L} rows "
+                      f"for q {tuple(q.shape)}")
+    dev = q.device
+    for t in (q, k, v):
+        if t.dtype != torch.float32 or not t.is_cuda or t.device != dev or t.stride(-1) != 1:
+            raise WXError("decode_attention_f32_grouped: q, k and v must be float32 tensors on one HIP device with a "
+                          "contiguous head dim")
+    if out is None:
+        out = torch.empty((B, G, H, D), dtype=torch.float32, device=dev)
+    if tuple(out.shape) != (B, G, H, D) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+        raise WXError("decode_attention_f32_grouped: out must be a contiguous float32 [B, G, H, 64] tensor on the "
+                      "queries' device")
+    st = [(ctypes.c_int64 * 3)(*(int(x) for x in t.stride()[:3])) for t in (q, k, v)]
+    wsb = lib.wx_decode_attention_grouped_workspace_bytes(B, G, H, L)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        ws = _scratch.get("decode_attention_grouped", dev, wsb, stream)
+        _check(lib.wx_decode_attention_f32_grouped(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, G, H, L, D, st[0], st[1],
+                                                   st[2], float(scale), _ptr(ws), ws.numel(),
+                                                   ctypes.c_void_p(stream.cuda_stream)))
+    return out
+
+
+def beam_topk(logits: torch.Tensor, cum: torch.Tensor, G: int):
+    """wx_beam_topk: logits [B G, V] fp32 (any row stride >= V, columns contiguous) and the beams'
+    running sums cum [B G] -> (scores [B, 2G] fp32, index [B, 2G] int32 = g V + t): per chunk the 2G
+    best candidates cum + log_softmax(logits), best first, ties by lower g, higher logit, lower t.
+    On the current stream."""
+    lib = load()
+    G = int(G)
+    if logits.dim() != 2 or cum.dim() != 1 or G < 1 or logits.shape[0] % G or cum.shape[0] != logits.shape[0]:
+        raise WXError(f"beam_topk: logits {tuple(logits.shape)} / cum {tuple(cum.shape)} are not [B G, V] / [B G] for "
+                      f"G = {G}")
+    dev = logits.device
+    for t in (logits, cum):
+        if t.dtype != torch.float32 or not t.is_cuda or t.device != dev:
+            raise WXError("beam_topk: logits and cum must be float32 tensors on one HIP device")
+    if (logits.shape[1] > 1 and logits.stride(1) != 1) or not cum.is_contiguous():
+        raise WXError("beam_topk: the logits' columns and cum must be contiguous")
+    B, V = int(logits.shape[0]) // G, int(logits.shape[1])
+    scores = torch.empty((B, 2 * G), dtype=torch.float32, device=dev)
+    index = torch.empty((B, 2 * G), dtype=torch.int32, device=dev)
+    wsb = lib.wx_beam_topk_workspace_bytes(B, G, V)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        ws = _scratch.get("beam_topk", dev, wsb, stream)
+        _check(lib.wx_beam_topk(_ptr(logits), int(logits.stride(0)) if B * G > 1 else V, _ptr(cum), B, G, V,
+                                _ptr(scores), _ptr(index), _ptr(ws), ws.numel(), ctypes.c_void_p(stream.cuda_stream)))
+    return scores, index
 
 
 def sincnet_stage(x_tm: torch.Tensor, do_abs: bool, gamma, beta, eps: float, slope: float = 0.01,

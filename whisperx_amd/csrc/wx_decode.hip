@@ -157,6 +157,116 @@ __global__ __launch_bounds__(256) void decode_merge_kernel(const DecArgs a, int6
     a.o[bh * kHead + d] = out / Lsum;
 }
 
+// ------------------------------------------------------------------------------ grouped
+// The G queries of one batch entry (the beams of one audio chunk) share its keys and values: the
+// block loads its 2 x 128 rows once, as above, and then runs the per-query arithmetic of
+// decode_chunk_kernel G times on the rows it holds, expression for expression, so that row (b, g, h)
+// has the bits the ungrouped kernel gives that query.  The G queries wait in LDS (one 16-byte load
+// per lane of the first G 16-lane groups, issued behind the key / value loads); the 16 groups'
+// partials of every query go to LDS (G x 4.1 KB, sized by the launch) and wave w merges the queries
+// w, w + 4, ... in group order.  The workspace slots are those of B G H ungrouped rows, and
+// decode_merge_kernel merges the chunks.
+constexpr int kMaxGroup = WX_DECODE_ATTENTION_MAX_GROUP;
+
+struct GrpArgs {
+    DecArgs d;       // (qs unused: the grouped strides are qs3)
+    int64_t qs3[3];  // b, g, h
+    int32_t G;
+};
+
+__global__ __launch_bounds__(256) void decode_chunk_grouped_kernel(const GrpArgs ga) {
+    extern __shared__ __attribute__((aligned(16))) float s_dyn[];
+    const DecArgs& a = ga.d;
+    const int G = ga.G;
+    float* s_q = s_dyn;                        // [G][64]
+    float* s_acc = s_q + G * kHead;            // [G][16][64]
+    float* s_m = s_acc + G * kGroups * kHead;  // [G][16]
+    float* s_l = s_m + G * kGroups;            // [G][16]
+    const int c = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+    const int tid = threadIdx.x;
+    const int grp = tid >> 4, d4 = (tid & 15) * 4;
+    const int j0 = c * kChunk;
+    const int n = min(kChunk, a.L - j0);
+
+    const float* kb = a.k + (int64_t)b * a.ks[0] + (int64_t)h * a.ks[1] + (int64_t)j0 * a.ks[2] + d4;
+    const float* vb = a.v + (int64_t)b * a.vs[0] + (int64_t)h * a.vs[1] + (int64_t)j0 * a.vs[2] + d4;
+
+    float4 kr[kPasses], vr[kPasses];
+#pragma unroll
+    for (int i = 0; i < kPasses; ++i) {
+        const int r = kGroups * i + grp;
+        kr[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (r < n) kr[i] = *reinterpret_cast<const float4*>(kb + (int64_t)r * a.ks[2]);
+    }
+#pragma unroll
+    for (int i = 0; i < kPasses; ++i) {
+        const int r = kGroups * i + grp;
+        vr[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (r < n) vr[i] = *reinterpret_cast<const float4*>(vb + (int64_t)r * a.vs[2]);
+    }
+    if (grp < G)  // query grp of this (batch, head)
+        *reinterpret_cast<float4*>(s_q + grp * kHead + d4) = *reinterpret_cast<const float4*>(
+            a.q + (int64_t)b * ga.qs3[0] + (int64_t)grp * ga.qs3[1] + (int64_t)h * ga.qs3[2] + d4);
+    __syncthreads();
+
+    for (int g = 0; g < G; ++g) {
+        const float4 qv = *reinterpret_cast<const float4*>(s_q + g * kHead + d4);
+        float s[kPasses];
+        float m = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < kPasses; ++i) {
+            const float part = (qv.x * kr[i].x + qv.y * kr[i].y) + (qv.z * kr[i].z + qv.w * kr[i].w);
+            s[i] = kGroups * i + grp < n ? a.scale * row16_sum(part) : -INFINITY;
+            m = fmaxf(m, s[i]);
+        }
+        float l = 0.f;
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (m > -INFINITY) {
+#pragma unroll
+            for (int i = 0; i < kPasses; ++i) {
+                const float p = expf(s[i] - m);
+                l += p;
+                acc.x += p * vr[i].x;
+                acc.y += p * vr[i].y;
+                acc.z += p * vr[i].z;
+                acc.w += p * vr[i].w;
+            }
+        }
+        if ((tid & 15) == 0) {
+            s_m[g * kGroups + grp] = m;
+            s_l[g * kGroups + grp] = l;
+        }
+        *reinterpret_cast<float4*>(s_acc + (g * kGroups + grp) * kHead + d4) = acc;
+    }
+    __syncthreads();
+
+    // wave w, lane = dim: the queries w, w + 4, ..., each over its 16 groups in group order
+    const int d = tid & 63;
+    for (int g = tid >> 6; g < G; g += 4) {
+        const float* gm = s_m + g * kGroups;
+        const float* gl = s_l + g * kGroups;
+        const float* gacc = s_acc + g * kGroups * kHead;
+        float M = gm[0];
+#pragma unroll
+        for (int u = 1; u < kGroups; ++u) M = fmaxf(M, gm[u]);
+        float Lsum = 0.f, out = 0.f;
+#pragma unroll
+        for (int u = 0; u < kGroups; ++u) {
+            const float w = expf(gm[u] - M);
+            Lsum += w * gl[u];
+            out += w * gacc[u * kHead + d];
+        }
+        const int64_t bgh = ((int64_t)b * G + g) * a.H + h;
+        if (a.nc == 1) {
+            a.o[bgh * kHead + d] = out / Lsum;
+        } else {
+            const int64_t slot = bgh * a.nc + c;
+            if (d == 0) a.ml[slot] = make_float2(M, Lsum);
+            a.acc[slot * kHead + d] = out;
+        }
+    }
+}
+
 inline int64_t chunks(int32_t L) { return ((int64_t)L + kChunk - 1) / kChunk; }
 
 // The workspace's layout, stated once: measures on a null base, fills `a` on the caller's pointer.
@@ -214,6 +324,53 @@ extern "C" int wx_decode_attention_f32(const float* q, const float* k, const flo
     hipLaunchKernelGGL(decode_chunk_kernel, dim3((unsigned)a.nc, (unsigned)H, (unsigned)B), dim3(256), 0, st, a);
     if (a.nc > 1) {
         const int64_t BH = (int64_t)B * H;  // (<= 65535^2: the merge grid's x fits)
+        hipLaunchKernelGGL(decode_merge_kernel, dim3((unsigned)((BH + 3) / 4)), dim3(256), 0, st, a, BH);
+    }
+    return wx::launch_status();
+}
+
+extern "C" size_t wx_decode_attention_grouped_workspace_bytes(int32_t B, int32_t G, int32_t H, int32_t L) {
+    const bool ok = B > 0 && G >= 1 && G <= wxdec::kMaxGroup && B <= 65535;
+    return wxdec::carve(nullptr, ok ? B * G : 0, H, L, nullptr);
+}
+
+extern "C" int wx_decode_attention_f32_grouped(const float* q, const float* k, const float* v, float* o, int32_t B,
+                                               int32_t G, int32_t H, int32_t L, int32_t D, const int64_t* q_strides,
+                                               const int64_t* k_strides, const int64_t* v_strides, float scale,
+                                               void* workspace, size_t workspace_bytes, void* stream) {
+    using namespace wxdec;
+    if (B < 0 || G < 1 || G > kMaxGroup || H < 1 || L < 1 || D != kHead) return WX_E_INVALID;
+    if (B == 0) return WX_OK;
+    if (!q || !k || !v || !o || !q_strides || !k_strides || !v_strides || !workspace) return WX_E_INVALID;
+    for (const void* p : {(const void*)q, (const void*)k, (const void*)v, (const void*)o, (const void*)workspace})
+        if (reinterpret_cast<uintptr_t>(p) & 15) return WX_E_INVALID;
+    for (int i = 0; i < 3; ++i)
+        if (q_strides[i] % 4 || k_strides[i] % 4 || v_strides[i] % 4) return WX_E_INVALID;
+    if (B > 65535 || H > 65535) return WX_E_INVALID;  // grid y / z
+    if ((int64_t)B * G * H * chunks(L) > ((int64_t)1 << 40)) return WX_E_INVALID;
+    GrpArgs ga;
+    DecArgs& a = ga.d;
+    if (workspace_bytes < carve(workspace, B * G, H, L, &a)) return WX_E_WORKSPACE;
+    a.q = q;
+    a.k = k;
+    a.v = v;
+    a.o = o;
+    a.qs[0] = a.qs[1] = 0;
+    for (int i = 0; i < 3; ++i) {
+        ga.qs3[i] = q_strides[i];
+        a.ks[i] = k_strides[i];
+        a.vs[i] = v_strides[i];
+    }
+    ga.G = G;
+    a.H = H;
+    a.L = L;
+    a.nc = (int32_t)chunks(L);
+    a.scale = scale;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const size_t lds = (size_t)G * (kHead + kGroups * kHead + 2 * kGroups) * sizeof(float);  // (<= 35 KB)
+    hipLaunchKernelGGL(decode_chunk_grouped_kernel, dim3((unsigned)a.nc, (unsigned)H, (unsigned)B), dim3(256), lds, st, ga);
+    if (a.nc > 1) {
+        const int64_t BH = (int64_t)B * G * H;  // (<= 8 x 65535^2: the merge grid's x fits)
         hipLaunchKernelGGL(decode_merge_kernel, dim3((unsigned)((BH + 3) / 4)), dim3(256), 0, st, a, BH);
     }
     return wx::launch_status();

@@ -23,8 +23,11 @@ with its key / value cache, one position per step:
                 h = h + fc2(gelu(fc1(LN3 h)))                           wx_add_layernorm(want_sum)
     logits = LN_f(h) . embed_tokens^T
 
-Greedy decoding (beam_size 1, temperature 0) and language detection are built on it; beam search,
-temperature fallback, timestamps and the tokenizer are not.
+Greedy decoding (beam_size 1, temperature 0), beam search (asr.py:301-304: beam_size 5, patience 1,
+length_penalty 1 are the reference's defaults) and language detection are built on it.  In beam
+search the G beams of a chunk are rows b G + g of the state; their cross-attention reads the chunk's
+one K_x / V_x (wx_decode_attention_f32_grouped), and the 2G best continuations of every chunk come
+from wx_beam_topk.  Temperature fallback, timestamps and the tokenizer are not built.
 
 Without a GPU the same arithmetic runs in torch ops on the host (`F.conv1d`, `F.layer_norm`,
 `F.scaled_dot_product_attention`).  Both halves read their weights through one loader (`_Half`,
@@ -45,6 +48,7 @@ from . import _lib
 from .audio import log_mel_chunks
 
 _LN_EPS = 1e-5
+_MAX_BEAMS = _lib.DECODE_MAX_GROUP  # beams per chunk: the group size of wx_decode_attention_f32_grouped / wx_beam_topk
 
 
 # ---------------------------------------------------------------------- weights, for both halves
@@ -347,14 +351,27 @@ def load_whisper_encoder(path: str, device=None) -> WhisperEncoder:
 
 
 # ------------------------------------------------------------------------------------ decoder
+class Hypothesis(NamedTuple):
+    """One result of WhisperDecoder.beam_search: the generated ids (no prompt, no eot), the sum of
+    their log-probabilities (and eot's when the hypothesis ended on it), and
+    sum_logprob / n ** length_penalty over the n scored positions."""
+    ids: list
+    sum_logprob: float
+    score: float
+
+
 class DecoderState:
     """What `WhisperDecoder.start` returns and `step` advances: per layer the cross-attention keys
     and values (`cross`: [B, P, 2D], the k half then the v half of one GEMM), the self-attention
     caches (`self_k` / `self_v`: [B, H, max_target_positions, 64]) and `pos`, the tokens so far.
-    `stages`: the decoder's layers bound to these tensors, built at the first step."""
+    `stages`: the decoder's layers bound to these tensors, built at the first step.  With `G` > 1
+    beams per chunk (`start(beams=G)`) there are `rows` = B G sequences, row b G + g beam g of chunk
+    b: the caches are [B G, H, max_target_positions, 64] and `cross` stays [B, P, 2D], shared by a
+    chunk's beams."""
 
-    def __init__(self, B: int, P: int, cross, self_k, self_v, kernels: bool):
+    def __init__(self, B: int, P: int, cross, self_k, self_v, kernels: bool, beams: int = 1):
         self.B, self.P, self.pos = B, P, 0
+        self.G, self.rows = beams, B * beams
         self.cross, self.self_k, self.self_v = cross, self_k, self_v
         self.kernels = kernels
         self.stages = None
@@ -406,12 +423,18 @@ class WhisperDecoder:
         return torch.cuda.device(self.device) if self.device.type == "cuda" else contextlib.nullcontext()
 
     @torch.inference_mode()
-    def start(self, encoder_states: torch.Tensor, kernels: Optional[bool] = None) -> DecoderState:
+    def start(self, encoder_states: torch.Tensor, kernels: Optional[bool] = None, beams: int = 1) -> DecoderState:
         """encoder_states [B, P, D] (WhisperEncoder.encode's output) -> the state of a batch of B
         sequences at position 0: per layer one GEMM with [Wk_x; Wv_x] gives the cross-attention
         keys and values [B, P, 2D], which every step then reads in place, and the self-attention
         caches are allocated at [B, H, max_target_positions, 64].  `kernels`: the HIP route (the
-        default on a HIP device) or the same arithmetic in torch ops on the decoder's device."""
+        default on a HIP device) or the same arithmetic in torch ops on the decoder's device.
+        `beams` = G > 1: B G sequences, G per chunk (row b G + g), for beam search: the caches
+        have B G rows, the cross-attention keys and values stay [B, P, 2D] and a chunk's G beams
+        read them through wx_decode_attention_f32_grouped (an expanded view on the host route)."""
+        beams = int(beams)
+        if not 1 <= beams <= _MAX_BEAMS:
+            raise ValueError(f"WhisperDecoder.start: beams must lie in 1..{_MAX_BEAMS}, got {beams}")
         x = encoder_states
         if not torch.is_tensor(x) or x.dim() != 3 or x.shape[2] != self.D or x.shape[1] < 1:
             raise ValueError(f"WhisperDecoder.start: encoder_states must be [B, P, {self.D}], got "
@@ -423,10 +446,10 @@ class WhisperDecoder:
         B, P = int(x.shape[0]), int(x.shape[1])
         with self._ctx():
             cross = [F.linear(x, *L["kv_x"]) for L in self.layers]
-            shape = (B, self.H, self.max_target_positions, 64)
+            shape = (B * beams, self.H, self.max_target_positions, 64)
             self_k = [torch.zeros(shape, dtype=torch.float32, device=self.device) for _ in self.layers]
             self_v = [torch.zeros(shape, dtype=torch.float32, device=self.device) for _ in self.layers]
-        return DecoderState(B, P, cross, self_k, self_v, kernels)
+        return DecoderState(B, P, cross, self_k, self_v, kernels, beams)
 
     def _tokens(self, tokens, shape, who: str) -> torch.Tensor:
         """Token ids as an int64 tensor of `shape` on the decoder's device, every id in [0, V)."""
@@ -440,9 +463,10 @@ class WhisperDecoder:
 
     @torch.inference_mode()
     def step(self, state: DecoderState, tokens) -> torch.Tensor:
-        """One position for every row: tokens [B] (ids at position state.pos) -> the logits of the
-        next token [B, V] fp32, and the state moves on by one.  Runs on the current stream."""
-        return self._step(state, self._tokens(tokens, (state.B,), "step"))
+        """One position for every row: tokens [B] (ids at position state.pos; [B G] for a state of
+        G beams) -> the logits of the next token [B, V] fp32 ([B G, V]), and the state moves on by
+        one.  Runs on the current stream."""
+        return self._step(state, self._tokens(tokens, (state.rows,), "step"))
 
     def _step(self, st: DecoderState, tok: torch.Tensor) -> torch.Tensor:
         """step() on checked ids already on the device."""
@@ -460,20 +484,30 @@ class WhisperDecoder:
     def _stages(self, st: DecoderState) -> list:
         """The three stages of every layer on the state's tensors and route, at the position the
         state is at when they are called: both attentions on wx_decode_attention_f32 or on
-        torch's; the first writes the cache rows."""
-        B, P, D, H = st.B, st.P, self.D, self.H
+        torch's; the first writes the cache rows.  A state of G > 1 beams runs the self-attention
+        over its R = B G rows and the cross-attention of a chunk's G beams on the chunk's one
+        K / V: wx_decode_attention_f32_grouped, or torch's on a view expanded over the beams."""
+        B, G, R, P, D, H = st.B, st.G, st.rows, st.P, self.D, self.H
         if st.kernels:
             def attend(q, k, v, n=None):
-                return _lib.decode_attention_f32(q, k, v, 0.125, L=n).view(B, D)
+                return _lib.decode_attention_f32(q, k, v, 0.125, L=n).view(R, D)
+
+            def attend_beams(q, k, v):
+                return _lib.decode_attention_f32_grouped(q.view(B, G, H, 64), k, v, 0.125).view(R, D)
         else:
             def attend(q, k, v, n=None):
-                return F.scaled_dot_product_attention(q.unsqueeze(2), k[:, :, :n], v[:, :, :n], scale=0.125).reshape(B, D)
+                return F.scaled_dot_product_attention(q.unsqueeze(2), k[:, :, :n], v[:, :, :n], scale=0.125).reshape(R, D)
+
+            def attend_beams(q, k, v):  # k / v [B, H, P, 64] -> [B, G, H, P, 64]: a view, stride 0 over the beams
+                k, v = (t.unsqueeze(1).expand(B, G, H, P, 64) for t in (k, v))
+                return F.scaled_dot_product_attention(q.view(B, G, H, 1, 64), k, v, scale=0.125).reshape(R, D)
+        attend_x = attend if G == 1 else attend_beams
 
         def self_attention(L, ck, cv):
             def fn(y):
                 pos = st.pos
-                qkv = F.linear(y, *L["qkv"])  # [B, 3D]
-                q, k, v = (qkv[:, j * D:(j + 1) * D].view(B, H, 64) for j in range(3))
+                qkv = F.linear(y, *L["qkv"])  # [R, 3D]
+                q, k, v = (qkv[:, j * D:(j + 1) * D].view(R, H, 64) for j in range(3))
                 ck[:, :, pos].copy_(k)
                 cv[:, :, pos].copy_(v)
                 return F.linear(attend(q, ck, cv, pos + 1), *L["out"])
@@ -481,10 +515,31 @@ class WhisperDecoder:
 
         def cross_attention(L, kv):
             kx, vx = (kv[:, :, j * D:(j + 1) * D].view(B, P, H, 64).transpose(1, 2) for j in range(2))  # views, in place
-            return lambda y: F.linear(attend(F.linear(y, *L["q_x"]).view(B, H, 64), kx, vx), *L["out_x"])
+            return lambda y: F.linear(attend_x(F.linear(y, *L["q_x"]).view(R, H, 64), kx, vx), *L["out_x"])
 
         return [s for L, kv, ck, cv in zip(self.layers, st.cross, st.self_k, st.self_v)
                 for s in ((L["ln1"], self_attention(L, ck, cv)), (L["ln2"], cross_attention(L, kv)), (L["ln3"], _mlp(L)))]
+
+    @torch.inference_mode()
+    def reorder(self, state: DecoderState, parents) -> None:
+        """Row r of every self-attention cache (positions < state.pos) becomes row parents[r]:
+        `parents` are B G int64 ids in [0, B G), the rows the new beams continue.  A copy in place
+        (a gather, then a copy back: 2 x 2 x layers x B G x state.pos x D x 4 bytes read and as many
+        written); the stages stay bound to the same tensors.  The identity is a no-op."""
+        t = parents if torch.is_tensor(parents) else torch.as_tensor(parents)
+        if tuple(t.shape) != (state.rows,) or t.dtype.is_floating_point or t.dtype == torch.bool:
+            raise ValueError(f"WhisperDecoder.reorder: parents must be {state.rows} integer row ids, got {t.dtype} "
+                             f"{tuple(t.shape)}")
+        host = t.cpu().tolist()
+        if any(not 0 <= p < state.rows for p in host):
+            raise ValueError(f"WhisperDecoder.reorder: parents must lie in [0, {state.rows})")
+        if host == list(range(state.rows)) or state.pos == 0:
+            return
+        idx = t.to(device=self.device, dtype=torch.int64)
+        with self._ctx():
+            for cache in (*state.self_k, *state.self_v):
+                live = cache[:, :, :state.pos]
+                live.copy_(live.index_select(0, idx))
 
     @torch.inference_mode()
     def logits(self, encoder_states: torch.Tensor, tokens, kernels: Optional[bool] = None) -> torch.Tensor:
@@ -511,7 +566,8 @@ class WhisperDecoder:
 
     @torch.inference_mode()
     def generate(self, encoder_states: torch.Tensor, prompt, eot: int, max_length: int = 448, suppress_tokens=(),
-                 suppress_at_start=(), kernels: Optional[bool] = None) -> list:
+                 suppress_at_start=(), kernels: Optional[bool] = None, beam_size: int = 1, patience: float = 1.0,
+                 length_penalty: float = 1.0) -> list:
         """Greedy decoding (asr.py:53-62 at beam_size 1, temperature 0): `prompt` (a list of ids,
         the same for every row) is fed one id per step; then every step takes the argmax of the
         logits with `suppress_tokens` at -inf, and at the first generated position also
@@ -519,7 +575,12 @@ class WhisperDecoder:
         finished rows are fed `eot` and their output ignored.  The loop ends when every row is done
         or prompt + generated ids number min(max_length, max_target_positions).  Returns the
         generated ids per row, without the prompt and without `eot`.  The completion check
-        synchronises once per step."""
+        synchronises once per step.  `beam_size` > 1: the ids of beam_search's best hypothesis of
+        every row (`patience` and `length_penalty` are beam_search's; greedy decoding ignores them)."""
+        if int(beam_size) != 1:
+            hyps = self.beam_search(encoder_states, prompt, eot, beam_size, patience, length_penalty, max_length,
+                                    suppress_tokens, suppress_at_start, kernels)
+            return [h[0].ids if h else [] for h in hyps]
         prompt = [int(t) for t in prompt]
         eot = int(eot)
         if not prompt:
@@ -551,6 +612,122 @@ class WhisperDecoder:
         out = []
         for row in torch.stack(steps, 1).cpu().tolist():
             out.append(row[:row.index(eot)] if eot in row else row)
+        return out
+
+    def _select(self, lg: torch.Tensor, cum: torch.Tensor, G: int, kernels: bool):
+        """wx_beam_topk's definition: per chunk the 2G best of cum[r] + log_softmax(lg[r])[t] as
+        (scores [B, 2G] fp32, index [B, 2G] int32 = g V + t), by score descending, then lower g,
+        higher logit, lower t.  The host route preselects 2G per row by logit as the kernel does."""
+        if kernels:
+            return _lib.beam_topk(lg, cum, G)
+        R, V = int(lg.shape[0]), int(lg.shape[1])
+        K = 2 * G
+        x, t = torch.sort(lg, dim=1, descending=True, stable=True)  # (logit descending, t ascending)
+        x, t = x[:, :K], t[:, :K]
+        sc = cum[:, None] + (x - torch.logsumexp(lg, 1)[:, None])
+        sc = torch.where((x == float("-inf")) | (cum[:, None] == float("-inf")), float("-inf"), sc)
+        idx = (torch.arange(R, device=lg.device)[:, None] % G) * V + t  # rows of a chunk: g ascending
+        sc, order = torch.sort(sc.view(R // G, G * K), dim=1, descending=True, stable=True)
+        return sc[:, :K], idx.view(R // G, G * K).gather(1, order)[:, :K].to(torch.int32)
+
+    @torch.inference_mode()
+    def beam_search(self, encoder_states: torch.Tensor, prompt, eot: int, beam_size: int = 5, patience: float = 1.0,
+                    length_penalty: float = 1.0, max_length: int = 448, suppress_tokens=(), suppress_at_start=(),
+                    kernels: Optional[bool] = None) -> list:
+        """Beam search (asr.py:301-304: the reference's default is beam_size 5, patience 1,
+        length_penalty 1).  The structure is that of OpenAI's BeamSearchDecoder and
+        MaximumLikelihoodRanker; this docstring is the specification.
+
+        G = beam_size beams per chunk are fed the prompt.  At the first generated step only beam 0
+        of a chunk is live (running sum 0; the others -inf).  Every step masks the logits as
+        generate does, takes the chunk's 2G best candidates (beam g, token t) by
+        sum[g] + log_softmax(logits[g])[t] (wx_beam_topk's order) and walks them best first until G
+        live beams are chosen: a candidate whose token is `eot` becomes a finished hypothesis (its
+        sum the candidate's score, its ids the beam's generated ids) unless the chunk already has
+        max(1, round(beam_size patience)) of them; any other becomes the next live beam.  At most
+        G of the candidates are `eot` (one per beam), so 2G suffice.  A chunk with that many
+        finished hypotheses is done: its rows are fed `eot` and ignored.  The loop ends when every
+        chunk is done or prompt + generated ids number min(max_length, max_target_positions); live
+        beams then fill a chunk's list up to beam_size, in order of their sums.
+
+        Returns per chunk its hypotheses, best first, as Hypothesis(ids, sum_logprob, score):
+        score = sum / n ** length_penalty with n the scored positions (the ids, plus one for an
+        `eot`; at least 1), ranked by score, earlier-found first on ties.  The self-attention
+        caches follow the beams by `reorder`; the 2G scores and indices of every chunk are the one
+        host synchronisation of a step."""
+        prompt = [int(t) for t in prompt]
+        eot, G = int(eot), int(beam_size)
+        if not prompt:
+            raise ValueError("WhisperDecoder.beam_search: the prompt is empty")
+        if not 0 <= eot < self.V:
+            raise ValueError(f"WhisperDecoder.beam_search: eot {eot} is outside the vocabulary of {self.V}")
+        if not 1 <= G <= _MAX_BEAMS:
+            raise ValueError(f"WhisperDecoder.beam_search: beam_size must lie in 1..{_MAX_BEAMS}, got {beam_size}")
+        if not float(patience) > 0:
+            raise ValueError(f"WhisperDecoder.beam_search: patience must be positive, got {patience}")
+        if self.V < 2 * G:
+            raise ValueError(f"WhisperDecoder.beam_search: a vocabulary of {self.V} is smaller than 2 x beam_size")
+        always, first = self._id_list(suppress_tokens, "suppress_tokens"), self._id_list(suppress_at_start, "suppress_at_start")
+        max_finished = max(1, round(G * float(patience)))
+        st = self.start(encoder_states, kernels, beams=G)
+        B, R, V = st.B, st.rows, self.V
+        limit = min(int(max_length), self.max_target_positions)
+        if B == 0 or len(prompt) >= limit:
+            return [[] for _ in range(B)]
+        ptok = self._tokens(torch.tensor(prompt).unsqueeze(0).expand(R, -1), (R, len(prompt)), "beam_search")
+        for i in range(len(prompt)):
+            lg = self._step(st, ptok[:, i])
+        ninf = float("-inf")
+        sums = [[0.0] + [ninf] * (G - 1) for _ in range(B)]
+        ids = [[[] for _ in range(G)] for _ in range(B)]
+        finished = [[] for _ in range(B)]  # (ids, sum, n) in the order found
+        steps = 0
+        identity = list(range(R))
+        while True:
+            if always is not None:
+                lg.index_fill_(1, always, ninf)
+            if first is not None and not steps:
+                lg.index_fill_(1, first, ninf)
+            cum = torch.tensor([x for row in sums for x in row], dtype=torch.float32).to(self.device)
+            with self._ctx():
+                sc, idx = self._select(lg, cum, G, st.kernels)
+                both = torch.cat([sc, idx.view(torch.float32)], 1).cpu()  # one synchronisation
+            sc, idx = both[:, :2 * G].tolist(), both[:, 2 * G:].contiguous().view(torch.int32).tolist()
+            steps += 1
+            parents, feed = list(identity), [eot] * R
+            for b in range(B):
+                if len(finished[b]) >= max_finished:
+                    continue
+                live = []  # (parent beam, token, sum)
+                for s, i in zip(sc[b], idx[b]):
+                    g, t = divmod(i, V)
+                    if t == eot:
+                        if len(finished[b]) < max_finished:
+                            finished[b].append((list(ids[b][g]), s, len(ids[b][g]) + 1))
+                    else:
+                        live.append((g, t, s))
+                        if len(live) == G:
+                            break
+                ids[b] = [ids[b][g] + [t] for g, t, _ in live]
+                sums[b] = [s for _, _, s in live]
+                for j, (g, t, _) in enumerate(live):
+                    parents[b * G + j], feed[b * G + j] = b * G + g, t
+            done = all(len(f) >= max_finished for f in finished)
+            if len(prompt) + steps >= limit or done:
+                break
+            if parents != identity:
+                self.reorder(st, torch.tensor(parents, dtype=torch.int64))
+            lg = self._step(st, torch.tensor(feed, dtype=torch.int64).to(self.device))
+        out = []
+        for b in range(B):
+            hyps = list(finished[b])
+            if len(hyps) < max_finished:  # not done: the live beams, already in order of their sums
+                for g in range(len(ids[b])):
+                    if len(hyps) >= G:
+                        break
+                    hyps.append((ids[b][g], sums[b][g], max(1, len(ids[b][g]))))
+            ranked = [Hypothesis(i, s, s / n ** float(length_penalty)) for i, s, n in hyps]
+            out.append(sorted(ranked, key=lambda h: -h.score))  # (stable: earlier-found first on ties)
         return out
 
     @torch.inference_mode()
