@@ -30,6 +30,9 @@
  *   wx_whisper_stem   <- whisperx/asr.py:77-86  WhisperModel.encode (the audio encoder's two
  *                        convolutions, GELUs and positional table, fused; the layers above it
  *                        run on wx_attention_f32 and wx_add_layernorm)
+ *   wx_attention_h16, wx_add_layernorm_h16 <- whisperx/asr.py:262  compute_type="float16" (the
+ *                        same encoder layers on fp16 / bf16 GEMMs and attention, the residual
+ *                        stream and the norms in fp32)
  *   wx_decode_attention_f32 <- whisperx/asr.py:53-62, 245-257  generate_segment_batched and
  *                        detect_language (the text decoder's self- and cross-attention of one
  *                        decode step: one query row per sequence and head)
@@ -264,6 +267,26 @@ int wx_attention_f32(const float* q, const float* k, const float* v, float* o, i
                      int32_t D, const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
                      float scale, void* stream);
 
+/* The same attention on 16-bit inputs (asr.py:262: the reference loads Whisper with
+ * compute_type="float16"; the half route of WhisperEncoder): q/k/v are [B, H, T, 64] views of fp16
+ * (dtype WX_DTYPE_F16) or bf16 (WX_DTYPE_BF16) elements with element strides {batch, head, time},
+ * every stride a multiple of 8 and every pointer 16-byte aligned — the three slices of a fused
+ * [B, T, 3 * 64 H] GEMM output are read in place; o is [B, T, H, 64] contiguous in the same type.
+ * T >= 1; no workspace.  Scores are accumulated in fp32 from the 16-bit operands
+ * (v_mfma_f32_32x32x16_{f16,bf16}); scale, running maximum, exponentials and running sum are fp32;
+ * the unnormalised probabilities are rounded (to nearest even) to the element type as the operand
+ * of the second MFMA, and the running sum is taken over those ROUNDED probabilities; O is
+ * accumulated in fp32, divided by the sum in fp32 and rounded once on the store.  K / V rows at and
+ * past T enter the arithmetic as zeros and no address outside the tensors is loaded from.  Row
+ * (b, h, t) does not depend on B.  Validation, before anything is enqueued: B < 0, H < 1, T < 1,
+ * D != 64 or an unknown dtype is WX_E_INVALID; then B == 0 is WX_OK; then a null or misaligned
+ * pointer, a stride that is no multiple of 8 or more than 2^31 - 1 workgroups is WX_E_INVALID. */
+#define WX_DTYPE_F16  1
+#define WX_DTYPE_BF16 2
+int wx_attention_h16(const void* q, const void* k, const void* v, void* o, int32_t B, int32_t H, int32_t T,
+                     int32_t D, const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                     float scale, int32_t dtype, void* stream);
+
 /* The same attention over nseg segments packed back to back in one launch (the emission
  * producer's packed encoder: every segment's rows in one [rows, H, 64] batch, each segment
  * attending only to itself — the reference's one-unpadded-forward-per-segment semantics,
@@ -298,6 +321,18 @@ int wx_posconv_packed(const float* h, int32_t D, const float* w_packed, const fl
  * fp32 tolerance (torch uses Welford), not bit-identical. */
 int wx_add_layernorm(const float* a, const float* b, int64_t rows, int32_t D, int64_t a_stride, int64_t b_stride,
                      const float* gamma, const float* beta, float eps, float* y, float* sum_out, void* stream);
+
+/* wx_add_layernorm between the fp32 residual stream and the 16-bit GEMMs of WhisperEncoder's half
+ * route: s = a + float(b) with b [rows] x D elements of `dtype` (WX_DTYPE_F16 / WX_DTYPE_BF16; row
+ * stride b_stride elements, a multiple of 8), or s = a when b is NULL (the first norm of the chain).
+ * Mean, biased variance and the normalisation are wx_add_layernorm's, expression for expression, in
+ * fp32; y is [rows][D] of `dtype`, rounded (to nearest even) on the store: bit for bit the rounding
+ * of wx_add_layernorm(a, float(b))'s y.  sum_out (fp32, may be NULL) receives s.  Widths, alignment
+ * rules (a_stride a multiple of 4; all pointers 16-byte aligned) and the validation order are
+ * wx_add_layernorm's, with the dtype checked beside D. */
+int wx_add_layernorm_h16(const float* a, const void* b, int64_t rows, int32_t D, int64_t a_stride, int64_t b_stride,
+                         const float* gamma, const float* beta, float eps, int32_t dtype, void* y, float* sum_out,
+                         void* stream);
 
 /* VAD producer (vad.py:198-240 -> pyannote SincNet): the epilogue of one SincNet stage on the
  * time-major conv output x [B windows][L][C] (window stride x_window_stride elements, row

@@ -17,6 +17,14 @@ difference has to exceed), a repetition being every chunk in batches of --batch-
 The stem arm also reports what the algorithm needs from the shapes: FLOP (2 x 3 x (n_mels + D) x D
 per input / output row pair) over the fp32 MFMA peak as a share of the measured time.  Prints one
 JSON line; --out writes it to a file (profiles/whisper_encoder_<host>.json).
+
+--dtype float16 | bfloat16 measures the half route instead (profiles/whisper_encoder_half_<host>.json):
+  attention   B 16, T 1500, H 8 and H 20 on the three views of a fused [B, T, 3 x 64 H] buffer of
+              that type, between device events over --steps launches: wx_attention_h16, torch's
+              scaled_dot_product_attention on the same views, and wx_attention_f32 on fp32 copies of
+              them; each with its TFLOP/s for 4 T^2 64 B H and its share of the 16-bit MFMA peak
+  encode      per geometry: WhisperEncoder(dtype).encode, this repository's fp32 encode in the same
+              run, and transformers' WhisperEncoder cast to the type (sdpa), same device and batches
 """
 from __future__ import annotations
 
@@ -31,9 +39,90 @@ if ROOT not in sys.path:
 from benchlib import beats, event_timed, timed  # noqa: E402
 
 F32_MFMA_PEAK_FLOPS = 157.3e12  # MI355X v_mfma_f32_*_f32, spec
+H16_MFMA_PEAK_FLOPS = 2.5e15    # MI355X dense f16 / bf16 MFMA, spec
 GEOMETRIES = {"base": {"D": 512, "layers": 6, "n_mels": 80, "chunks": 151},
               "large-v2": {"D": 1280, "layers": 32, "n_mels": 80, "chunks": 32}}
 P = 1500
+
+
+def half_main(args):
+    """The --dtype float16 / bfloat16 record."""
+    import torch
+    import torch.nn.functional as F
+    from transformers import WhisperConfig
+    from transformers.models.whisper.modeling_whisper import WhisperEncoder as HFEncoder
+
+    from whisperx_amd import WhisperEncoder, _lib
+
+    if not torch.cuda.is_available():
+        raise SystemExit("whisper_encoder_bench: needs a HIP device")
+    dtype = getattr(torch, args.dtype)
+    dev = torch.device("cuda", 0)
+    sync = torch.cuda.synchronize
+    bs = args.batch_size
+    result = {"tool": "tools/whisper_encoder_bench.py", "device": torch.cuda.get_device_name(0),
+              "lib": os.path.basename(_lib.LIB_PATH), "batch_size": bs, "dtype": args.dtype,
+              "peaks": {"f32_mfma_flop_per_s": F32_MFMA_PEAK_FLOPS, "h16_mfma_flop_per_s": H16_MFMA_PEAK_FLOPS},
+              "attention": {}, "geometries": {}}
+    torch.manual_seed(args.seed)
+    for H in (8, 20):
+        B, D = 16, 64 * H
+        qkv = torch.randn((B, P, 3 * D), device=dev).to(dtype)
+        q, k, v = (qkv[..., j * D:(j + 1) * D].view(B, P, H, 64).transpose(1, 2) for j in range(3))
+        q32, k32, v32 = (t.float() for t in (q, k, v))
+        flop = 4 * P * P * 64 * B * H
+        arms = {"wx_attention_h16": lambda i: _lib.attention_h16(q, k, v, 0.125),
+                "sdpa": lambda i: F.scaled_dot_product_attention(q, k, v, scale=0.125),
+                "wx_attention_f32": lambda i: _lib.attention_f32(q32, k32, v32, 0.125)}
+        r = {"shape": {"B": B, "H": H, "T": P, "flop": flop}}
+        with torch.inference_mode():
+            ref = F.scaled_dot_product_attention(q, k, v, scale=0.125).transpose(1, 2).float()
+            r["max_abs_diff_h16_vs_sdpa"] = float((_lib.attention_h16(q, k, v, 0.125).float() - ref).abs().max())
+            for arm, fn in arms.items():
+                t = event_timed(fn, args.repeat, args.warmup, args.steps, torch)
+                t["tflop_per_s"] = flop / t["median_s"] / 1e12
+                t["h16_mfma_peak_share"] = flop / t["median_s"] / H16_MFMA_PEAK_FLOPS
+                r[arm] = t
+        r["h16_vs_sdpa"] = beats(r["wx_attention_h16"], r["sdpa"])
+        r["h16_vs_f32"] = beats(r["wx_attention_h16"], r["wx_attention_f32"])
+        result["attention"][f"H{H}"] = r
+        del qkv, q, k, v, q32, k32, v32, ref
+        torch.cuda.empty_cache()
+    for name in args.geometries.split(","):
+        g = GEOMETRIES[name]
+        D, M, B = g["D"], g["n_mels"], g["chunks"]
+        torch.manual_seed(args.seed)
+        cfg = WhisperConfig(d_model=D, encoder_layers=g["layers"], encoder_attention_heads=D // 64, encoder_ffn_dim=4 * D,
+                            num_mel_bins=M, max_source_positions=P, decoder_layers=1, decoder_attention_heads=1,
+                            decoder_ffn_dim=64, vocab_size=64, pad_token_id=0, bos_token_id=1, eos_token_id=2,
+                            decoder_start_token_id=1, attn_implementation="sdpa")
+        hf = HFEncoder(cfg).eval().to(dev)
+        for p in hf.parameters():
+            p.requires_grad_(False)
+        ours32, ours = WhisperEncoder(hf, device=dev), WhisperEncoder(hf, device=dev, dtype=dtype)
+        hf = hf.to(dtype)
+        x = 0.5 * torch.randn((B, M, 2 * P), device=dev) - 0.5
+        xh = x.to(dtype)
+        r = {"shape": {**g, "frames_per_chunk": 2 * P, "positions": P, "attn_implementation": cfg._attn_implementation}}
+
+        def hf_arm():
+            with torch.inference_mode():
+                return torch.cat([hf(xh[a:a + bs]).last_hidden_state for a in range(0, B, bs)])
+
+        got, got32, want = ours.encode(x, batch_size=bs), ours32.encode(x, batch_size=bs), hf_arm()
+        sync()
+        r["max_abs_diff_half_vs_fp32"] = float((got - got32).abs().max())
+        r["max_abs_diff_hf_half_vs_fp32"] = float((want.float() - got32).abs().max())
+        del got, got32, want
+        r["ours_half"] = timed(lambda: ours.encode(x, batch_size=bs), args.repeat, args.warmup, sync)
+        r["ours_fp32"] = timed(lambda: ours32.encode(x, batch_size=bs), args.repeat, args.warmup, sync)
+        r["hf_half"] = timed(hf_arm, args.repeat, args.warmup, sync)
+        r["half_vs_fp32"] = beats(r["ours_half"], r["ours_fp32"])
+        r["half_vs_hf_half"] = beats(r["ours_half"], r["hf_half"])
+        result["geometries"][name] = r
+        del hf, ours, ours32, x, xh
+        torch.cuda.empty_cache()
+    return result
 
 
 def main():
@@ -45,7 +134,10 @@ def main():
     ap.add_argument("--steps", type=int, default=10, help="stem launches per stem-arm repetition")
     ap.add_argument("--seed", type=int, default=12)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--dtype", choices=("float32", "float16", "bfloat16"), default="float32")
     args = ap.parse_args()
+    if args.dtype != "float32":
+        return emit(half_main(args), args.out)
     import torch
     import torch.nn.functional as F
     from transformers import WhisperConfig
@@ -106,11 +198,14 @@ def main():
         result["geometries"][name] = r
         del hf, ours, x, out
         torch.cuda.empty_cache()
-    line = json.dumps(result)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
+    emit(result, args.out)
+
+
+def emit(result, out):
+    print(json.dumps(result))
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
             f.write(json.dumps(result, indent=1) + "\n")
 
 

@@ -25,7 +25,8 @@ SRC_PATH = os.path.join(_HERE, "csrc", "wx_align.hip")
 SRC_PATHS = [SRC_PATH, os.path.join(_HERE, "csrc", "wx_binarize.hip"), os.path.join(_HERE, "csrc", "wx_emission.hip"),
              os.path.join(_HERE, "csrc", "wx_vad.hip"), os.path.join(_HERE, "csrc", "wx_diarize.hip"),
              os.path.join(_HERE, "csrc", "wx_mel.hip"), os.path.join(_HERE, "csrc", "wx_whisper.hip"),
-             os.path.join(_HERE, "csrc", "wx_decode.hip"), os.path.join(_HERE, "csrc", "wx_beam.hip")]
+             os.path.join(_HERE, "csrc", "wx_decode.hip"), os.path.join(_HERE, "csrc", "wx_beam.hip"),
+             os.path.join(_HERE, "csrc", "wx_attention_h16.hip")]
 INST_PATH = os.path.join(_HERE, "csrc", "wx_align_inst.hip")
 HDR_PATHS = sorted(glob.glob(os.path.join(_HERE, "csrc", "*.h"))) + [INST_PATH]  # (a new header: a rebuild)
 INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
@@ -113,6 +114,8 @@ SIGNATURES = {
                                                        _vp, _sz, _vp]),
     "wx_beam_topk_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "wx_beam_topk": (ctypes.c_int, [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "wx_attention_h16": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _i32, _vp]),
+    "wx_add_layernorm_h16": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _f32, _i32, _vp, _vp, _vp]),
 }
 
 
@@ -982,6 +985,61 @@ def attention_f32(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: floa
         _check(lib.wx_attention_f32(_ptr(q), _ptr(k), _ptr(v), _ptr(o), B, H, T, D, st[0], st[1], st[2],
                                     float(scale), _stream(q.device)))
     return o
+
+
+# wx_attention_h16 / wx_add_layernorm_h16's dtype argument (include/wx_align.h WX_DTYPE_*)
+HALF_DTYPES = {torch.float16: 1, torch.bfloat16: 2}
+
+
+def attention_h16(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float) -> torch.Tensor:
+    """wx_attention_h16: softmax(scale * q k^T) v for [B, H, T, 64] fp16 or bf16 device views of one
+    dtype (head dim contiguous, batch / head / time strides multiples of 8, 16-byte aligned: the
+    slices of a fused q/k/v GEMM output as they are).  Returns [B, T, H, 64] in that dtype on the
+    current stream."""
+    lib = load()
+    code = HALF_DTYPES.get(q.dtype)
+    if code is None or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise WXError(f"attention_h16: q/k/v must share one of float16 / bfloat16, got {q.dtype}, {k.dtype}, {v.dtype}")
+    B, H, T, D = (int(x) for x in q.shape)
+    if tuple(k.shape) != (B, H, T, D) or tuple(v.shape) != (B, H, T, D):
+        raise WXError(f"attention_h16: q/k/v shapes differ ({tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)})")
+    if any(t.stride(3) != 1 for t in (q, k, v)) and D > 1:
+        raise WXError("attention_h16: the head dim must be contiguous")
+    o = torch.empty((B, T, H, D), dtype=q.dtype, device=q.device)
+    st = [(ctypes.c_int64 * 3)(*(int(x) for x in t.stride()[:3])) for t in (q, k, v)]
+    with torch.cuda.device(q.device):
+        _check(lib.wx_attention_h16(_ptr(q), _ptr(k), _ptr(v), _ptr(o), B, H, T, D, st[0], st[1], st[2],
+                                    float(scale), code, _stream(q.device)))
+    return o
+
+
+def add_layernorm_h16(a: torch.Tensor, b: Optional[torch.Tensor], gamma: torch.Tensor, beta: torch.Tensor, eps: float,
+                      dtype: torch.dtype, want_sum: bool = False):
+    """wx_add_layernorm_h16: LayerNorm(a + float(b)) over the last dim, a fp32 and b of `dtype`
+    (float16 / bfloat16) of one shape, or LayerNorm(a) with b None; the norm is computed in fp32
+    and y is rounded to `dtype`.  Returns y, or (y, a + float(b)) with want_sum (the sum is fp32)."""
+    lib = load()
+    code = HALF_DTYPES.get(dtype)
+    if code is None or a.dtype != torch.float32 or (b is not None and b.dtype != dtype):
+        raise WXError(f"add_layernorm_h16: a must be float32 and b float16 / bfloat16 as `dtype` says, got {a.dtype}, "
+                      f"{None if b is None else b.dtype}, dtype {dtype}")
+    D = int(a.shape[-1])
+    if b is not None and tuple(a.shape) != tuple(b.shape):
+        raise WXError(f"add_layernorm_h16: shapes differ ({tuple(a.shape)}, {tuple(b.shape)})")
+
+    def rows_of(t, mult):  # 16-byte aligned rows, or a contiguous copy (as add_layernorm)
+        t = t.reshape(-1, D)
+        return t if t.data_ptr() % 16 == 0 and (t.shape[0] <= 1 or t.stride(0) % mult == 0) and t.stride(1) == 1 \
+            else t.contiguous()
+    a2, b2 = rows_of(a, 4), None if b is None else rows_of(b, 8)
+    rows = int(a2.shape[0])
+    y = torch.empty(a.shape, dtype=dtype, device=a.device)
+    s = torch.empty(a.shape, dtype=torch.float32, device=a.device) if want_sum else None
+    with torch.cuda.device(a.device):
+        _check(lib.wx_add_layernorm_h16(_ptr(a2), _ptr(b2), rows, D, int(a2.stride(0)) if rows else D,
+                                        int(b2.stride(0)) if rows and b2 is not None else D, _ptr(gamma), _ptr(beta),
+                                        float(eps), code, _ptr(y), _ptr(s), _stream(a.device)))
+    return (y, s) if want_sum else y
 
 
 class PackedSegments:

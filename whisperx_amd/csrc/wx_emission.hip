@@ -651,6 +651,81 @@ __global__ __launch_bounds__(256) void add_ln_kernel(const float* __restrict__ a
     }
 }
 
+// add_ln_kernel between WhisperEncoder's fp32 residual stream and its 16-bit GEMMs
+// (wx_add_layernorm_h16): b holds fp16 / bf16 elements (BF) and is widened on the load (a null b:
+// zeros, added like any other, so that the result is add_ln_kernel's on a zero b), y is rounded
+// to nearest even on the store, the sum stays fp32.  Everything between is add_ln_kernel's,
+// expression for expression: y is bit for bit the rounding of its y.
+template <bool BF>
+__device__ __forceinline__ float ln_widen16(unsigned short x) {
+    if constexpr (BF) return __uint_as_float((unsigned)x << 16);
+    else return (float)__builtin_bit_cast(_Float16, x);
+}
+template <bool BF>
+__device__ __forceinline__ unsigned short ln_round16(float x) {
+    if constexpr (BF) return __builtin_bit_cast(unsigned short, (__bf16)x);
+    else return __builtin_bit_cast(unsigned short, (_Float16)x);
+}
+
+template <bool BF, int NV, int D4 = 64 * NV>
+__global__ __launch_bounds__(256) void add_ln_h16_kernel(const float* __restrict__ a, const unsigned short* __restrict__ b,
+                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                          float eps, int64_t rows, int64_t sa, int64_t sb, int64_t sy,
+                                                          unsigned short* __restrict__ y, float* __restrict__ sum_out) {
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int l = threadIdx.x & 63;
+    constexpr int D = 4 * D4;
+    constexpr bool kFull = D4 == 64 * NV;
+    static_assert(D4 <= 64 * NV && D4 > 64 * (NV - 1), "NV float4 per lane cover the row");
+    const float4* pa = reinterpret_cast<const float4*>(a + row * sa);
+    const ushort4* pb = b ? reinterpret_cast<const ushort4*>(b + row * sb) : nullptr;
+    float4 v[NV];
+    float acc = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        if (!kFull && 64 * i + l >= D4) {
+            v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            continue;
+        }
+        const float4 x = pa[64 * i + l];
+        float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (pb) {
+            const ushort4 u = pb[64 * i + l];
+            z = make_float4(ln_widen16<BF>(u.x), ln_widen16<BF>(u.y), ln_widen16<BF>(u.z), ln_widen16<BF>(u.w));
+        }
+        v[i] = make_float4(x.x + z.x, x.y + z.y, x.z + z.z, x.w + z.w);
+        acc += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    const float mean = acc / (float)D;
+    float q = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        if (!kFull && 64 * i + l >= D4) continue;
+        const float dx = v[i].x - mean, dy = v[i].y - mean, dz = v[i].z - mean, dw = v[i].w - mean;
+        q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
+    const float rstd = 1.0f / sqrtf(q / (float)D + eps);
+    ushort4* py = reinterpret_cast<ushort4*>(y + row * sy);
+    float4* ps = sum_out ? reinterpret_cast<float4*>(sum_out + row * sy) : nullptr;
+    const float4* pg = reinterpret_cast<const float4*>(gamma);
+    const float4* pt = reinterpret_cast<const float4*>(beta);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        if (!kFull && 64 * i + l >= D4) continue;
+        const float4 g = pg[64 * i + l], t = pt[64 * i + l];
+        py[64 * i + l] = make_ushort4(ln_round16<BF>((v[i].x - mean) * rstd * g.x + t.x),
+                                      ln_round16<BF>((v[i].y - mean) * rstd * g.y + t.y),
+                                      ln_round16<BF>((v[i].z - mean) * rstd * g.z + t.z),
+                                      ln_round16<BF>((v[i].w - mean) * rstd * g.w + t.w));
+        if (ps) ps[64 * i + l] = v[i];
+    }
+}
+
 // ------------------------------------------------------------------------------------
 // wav2vec2 positional convolution over packed segments (alignment.py:226-233: the encoder's
 // Wav2Vec2PositionalConvEmbedding — Conv1d(D, D, K = 128, padding K / 2, groups G), the last
@@ -986,6 +1061,45 @@ extern "C" int wx_add_layernorm(const float* a, const float* b, int64_t rows, in
         case 1280: hipLaunchKernelGGL(add_ln_kernel<5>, grid, dim3(256), 0, st, a, b, gamma, beta, eps, rows, a_stride, b_stride, (int64_t)D, y, sum_out); break;
         default: hipLaunchKernelGGL(add_ln_kernel<4>, grid, dim3(256), 0, st, a, b, gamma, beta, eps, rows, a_stride, b_stride, (int64_t)D, y, sum_out); break;
     }
+    return wx::launch_status();
+}
+
+extern "C" int wx_add_layernorm_h16(const float* a, const void* b, int64_t rows, int32_t D, int64_t a_stride,
+                                    int64_t b_stride, const float* gamma, const float* beta, float eps, int32_t dtype,
+                                    void* y, float* sum_out, void* stream) {
+    using namespace wxe;
+    if (rows < 0 || (D != 768 && D != 1024 && D != 512 && D != 256 && D != 384 && D != 1280) ||
+        (dtype != WX_DTYPE_F16 && dtype != WX_DTYPE_BF16))
+        return WX_E_INVALID;
+    if (rows == 0) return WX_OK;  // (an empty tensor may have no storage)
+    if (!a || !gamma || !beta || !y) return WX_E_INVALID;
+    if (a_stride < D || (a_stride & 3) || (b && (b_stride < D || (b_stride & 7)))) return WX_E_INVALID;
+    for (const void* p : {(const void*)a, b, (const void*)gamma, (const void*)beta, (const void*)y})
+        if (reinterpret_cast<uintptr_t>(p) & 15) return WX_E_INVALID;
+    if (sum_out && (reinterpret_cast<uintptr_t>(sum_out) & 15)) return WX_E_INVALID;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    const unsigned short* bh = static_cast<const unsigned short*>(b);
+    unsigned short* yh = static_cast<unsigned short*>(y);
+#define WX_LN16(BF, ...)                                                                                        \
+    hipLaunchKernelGGL((add_ln_h16_kernel<BF, __VA_ARGS__>), grid, dim3(256), 0, st, a, bh, gamma, beta, eps, rows, \
+                       a_stride, b_stride, (int64_t)D, yh, sum_out)
+#define WX_LN16_D(BF)                             \
+    switch (D) {                                  \
+        case 256: WX_LN16(BF, 1); break;          \
+        case 512: WX_LN16(BF, 2); break;          \
+        case 768: WX_LN16(BF, 3); break;          \
+        case 384: WX_LN16(BF, 2, 96); break;      \
+        case 1280: WX_LN16(BF, 5); break;         \
+        default: WX_LN16(BF, 4); break;           \
+    }
+    if (dtype == WX_DTYPE_BF16) {
+        WX_LN16_D(true)
+    } else {
+        WX_LN16_D(false)
+    }
+#undef WX_LN16_D
+#undef WX_LN16
     return wx::launch_status();
 }
 

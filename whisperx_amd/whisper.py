@@ -10,6 +10,16 @@ weights alone:
                 y = LN2(h);  h = h + fc2(gelu(fc1(y)))                   wx_add_layernorm(want_sum)
     out = LN_post(h)
 
+With `dtype` float16 or bfloat16 (asr.py:262: the reference's compute_type is "float16") the GEMMs,
+the GELU and the attention take and return that type, and nothing else does:
+
+    the stem, the residual stream h, the LayerNorm parameters and the positional table stay fp32;
+    every LayerNorm is computed in fp32 on the fp32 stream and its output rounded once to dtype
+                                                            wx_add_layernorm_h16
+    the q/k/v, out, fc1 and fc2 weights and biases are rounded once, at construction;
+    attention on the slices of the q/k/v GEMM's output      wx_attention_h16
+    a GEMM's output joins the stream as h + float(out); LN_post writes fp32.
+
 The result is what `WhisperForConditionalGeneration.generate(encoder_outputs=...)` accepts, and what
 `WhisperDecoder` below starts from.
 
@@ -150,10 +160,12 @@ def _device(device) -> torch.device:
 
 class _Taker:
     """take(name, shape): tensor `name` of `sd` as contiguous fp32 on `device`, its shape checked;
-    every refusal is a ValueError that names the class and the tensor."""
+    every refusal is a ValueError that names the class and the tensor.  With `gemm_dtype` (float16 /
+    bfloat16) the weights and biases of the Linear layers (`gemm`) come rounded to it, and one whose
+    rounding is not finite is refused."""
 
-    def __init__(self, sd: dict, device: torch.device, who: str):
-        self.sd, self.device, self.who = sd, device, who
+    def __init__(self, sd: dict, device: torch.device, who: str, gemm_dtype: Optional[torch.dtype] = None):
+        self.sd, self.device, self.who, self.gemm_dtype = sd, device, who, gemm_dtype
 
     def __call__(self, name, shape=None):
         t = self.sd.get(name)
@@ -164,9 +176,22 @@ class _Taker:
             raise ValueError(f"{self.who}: tensor '{name}' has shape {tuple(t.shape)}, expected {tuple(shape)}")
         return t
 
+    def gemm(self, name, shape=None):
+        """take(name, shape) of a Linear layer's weight or bias: in `gemm_dtype` when there is one."""
+        t = self(name, shape)
+        if self.gemm_dtype is None:
+            return t
+        r = t.to(self.gemm_dtype)
+        if not bool(torch.isfinite(r).all()):
+            raise ValueError(f"{self.who}: tensor '{name}' is not finite when rounded to "
+                             f"{str(self.gemm_dtype).replace('torch.', '')}")
+        return r
+
     def pair(self, prefix: str, n_out: int, n_in: Optional[int] = None):
         """(weight, bias) of the LayerNorm (n_out) or Linear (n_out x n_in) under `prefix`."""
-        return self(prefix + ".weight", (n_out,) if n_in is None else (n_out, n_in)), self(prefix + ".bias", (n_out,))
+        if n_in is None:
+            return self(prefix + ".weight", (n_out,)), self(prefix + ".bias", (n_out,))
+        return self.gemm(prefix + ".weight", (n_out, n_in)), self.gemm(prefix + ".bias", (n_out,))
 
     def layer_prefixes(self) -> list:
         """`layers.N.` for every layer of `sd`; the indices must be 0 .. n - 1."""
@@ -180,8 +205,8 @@ class _Taker:
         Whisper's k_proj does not have), (Wo, bo)."""
         if self.sd.get(p + ".k_proj.bias") is not None:
             raise ValueError(f"{self.who}: tensor '{p}.k_proj.bias' exists; Whisper's k_proj has no bias")
-        wq, wk, wv = (self(p + f".{n}_proj.weight", (D, D)) for n in "qkv")
-        bq, bv = self(p + ".q_proj.bias", (D,)), self(p + ".v_proj.bias", (D,))
+        wq, wk, wv = (self.gemm(p + f".{n}_proj.weight", (D, D)) for n in "qkv")
+        bq, bv = self.gemm(p + ".q_proj.bias", (D,)), self.gemm(p + ".v_proj.bias", (D,))
         return (torch.cat([wq, wk, wv], 0), torch.cat([bq, torch.zeros_like(bq), bv])), self.pair(p + ".out_proj", D, D)
 
     def table(self, name: str, rows: str, D: int) -> torch.Tensor:
@@ -193,9 +218,8 @@ class _Taker:
 
     def mlp(self, p: str, D: int):
         """fc1 and fc2 under the layer prefix `p`, the ffn width read from fc1."""
-        fc1 = self.table(p + "fc1.weight", "ffn", D)
-        ffn = int(fc1.shape[0])
-        return (fc1, self(p + "fc1.bias", (ffn,))), self.pair(p + "fc2", D, ffn)
+        ffn = int(self.table(p + "fc1.weight", "ffn", D).shape[0])
+        return self.pair(p + "fc1", ffn, D), self.pair(p + "fc2", D, ffn)
 
 
 # ----------------------------------------------------------------- the residual stream, for both
@@ -219,6 +243,25 @@ def _chain(h: torch.Tensor, stages: list, final, add_norm=None) -> torch.Tensor:
     return add_norm(h, stages[-1][1](y), *final, _LN_EPS) if stages else y
 
 
+def _chain_half(h: torch.Tensor, stages: list, final, dtype: torch.dtype, kernels: bool) -> torch.Tensor:
+    """_chain with 16-bit stages: the stream h and every norm are fp32, a norm's output is rounded
+    once to `dtype`, `fn` takes and returns `dtype`, and its result joins the stream as
+    h + float(fn(y)); the final norm writes fp32.  On the HIP route the first norm and every fused
+    add-norm but the last are wx_add_layernorm_h16; the last add is wx_add_layernorm on float(fn(y))."""
+    D = (h.shape[-1],)
+    if not kernels or not stages:
+        for ln, fn in stages:
+            h = h + fn(F.layer_norm(h, D, *ln, _LN_EPS).to(dtype)).float()
+        return F.layer_norm(h, D, *final, _LN_EPS)
+    y = _lib.add_layernorm_h16(h, None, *stages[0][0], _LN_EPS, dtype)
+    for (_, fn), (ln, _) in zip(stages, stages[1:]):
+        y, h = _lib.add_layernorm_h16(h, fn(y), *ln, _LN_EPS, dtype, want_sum=True)
+    return _lib.add_layernorm(h, stages[-1][1](y).float(), *final, _LN_EPS)
+
+
+_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
 class WhisperEncoder:
     """Whisper's audio encoder run from its weights.
 
@@ -229,11 +272,17 @@ class WhisperEncoder:
     D / 64 heads.  Anything that does not fit raises ValueError naming the tensor.  The derived
     weights (packed stem weights, [Wq; Wk; Wv] with a zero bias block for k) are built once here;
     the caller's module is read, never patched.  `device`: where the weights go (default: the
-    current HIP device when one is visible, else the CPU)."""
+    current HIP device when one is visible, else the CPU).  `dtype`: float32 (the default), or
+    float16 / bfloat16 for the half route of the module's docstring: the GEMM weights and biases are
+    rounded to it here (a float16 rounding that is not finite is a ValueError naming the tensor)
+    and only those copies are kept; `encode` returns fp32 either way."""
 
-    def __init__(self, weights, device=None):
-        self.device = _device(device)
-        take = _Taker(_state_dict(weights, _ENCODER), self.device, "WhisperEncoder")
+    def __init__(self, weights, device=None, dtype: torch.dtype = torch.float32):
+        if dtype not in _DTYPES:
+            raise ValueError(f"WhisperEncoder: dtype must be torch.float32, torch.float16 or torch.bfloat16, got {dtype!r}")
+        self.device, self.dtype = _device(device), dtype
+        take = _Taker(_state_dict(weights, _ENCODER), self.device, "WhisperEncoder",
+                      None if dtype == torch.float32 else dtype)
         w1 = take("conv1.weight")
         if w1.dim() != 3 or w1.shape[2] != 3:
             raise ValueError(f"WhisperEncoder: tensor 'conv1.weight' has shape {tuple(w1.shape)}, expected [D, n_mels, 3]")
@@ -309,11 +358,13 @@ class WhisperEncoder:
         """One slice [B, n_mels, 2 P] -> [B, P, D]: on the HIP route (stem, attention and the fused
         add-norms are kernels, the residual stream is [B P, D]) or in torch ops on x's device."""
         B, P, D, H = int(x.shape[0]), self.P, self.D, self.H
+        half = self.dtype != torch.float32
         if kernel:
             h = self.stem(x).reshape(B * P, D)
+            attention_kernel = _lib.attention_h16 if half else _lib.attention_f32
 
             def attend(q, k, v):
-                return _lib.attention_f32(q, k, v, 0.125).reshape(B * P, D)
+                return attention_kernel(q, k, v, 0.125).reshape(B * P, D)
         else:
             h = F.gelu(F.conv1d(x, self.w1, self.b1, padding=1))
             h = F.gelu(F.conv1d(h, self.w2, self.b2, stride=2, padding=1))
@@ -328,6 +379,8 @@ class WhisperEncoder:
             return F.linear(attend(q, k, v), *L["out"])
 
         stages = [s for L in self.layers for s in ((L["ln1"], lambda y, L=L: attention(y, L)), (L["ln2"], _mlp(L)))]
+        if half:
+            return _chain_half(h, stages, self.ln_post, self.dtype, kernel).view(B, P, D)
         return _chain(h, stages, self.ln_post, _lib.add_layernorm if kernel else None).view(B, P, D)
 
 
@@ -343,11 +396,11 @@ def _load_state_dict(path: str, who: str) -> dict:
     return sd
 
 
-def load_whisper_encoder(path: str, device=None) -> WhisperEncoder:
+def load_whisper_encoder(path: str, device=None, dtype: torch.dtype = torch.float32) -> WhisperEncoder:
     """A WhisperEncoder from a state-dict file: `.safetensors` through safetensors, anything else
     through torch.load(weights_only=True).  The file may hold a whole model; only the encoder's
-    tensors are used."""
-    return WhisperEncoder(_load_state_dict(path, "load_whisper_encoder"), device=device)
+    tensors are used.  `dtype`: WhisperEncoder's."""
+    return WhisperEncoder(_load_state_dict(path, "load_whisper_encoder"), device=device, dtype=dtype)
 
 
 # ------------------------------------------------------------------------------------ decoder
