@@ -39,6 +39,9 @@
  *   wx_decode_attention_f32_grouped, wx_beam_topk <- whisperx/asr.py:301-304  beam_size 5, the
  *                        reference's default (G beams of a chunk on the chunk's one cross-attention
  *                        K / V; the 2G best continuations of a chunk per step)
+ *   wx_decode_attention_h16, wx_decode_attention_h16_grouped <- whisperx/asr.py:262
+ *                        compute_type="float16" on the decoder (the two decode-step attentions
+ *                        on fp16 / bf16 caches and cross-attention keys / values)
  *
  * Conventions
  *   - All data pointers are DEVICE pointers (allocated by the caller; the library never
@@ -536,6 +539,32 @@ int wx_decode_attention_f32_grouped(const float* q, const float* k, const float*
                                     int32_t H, int32_t L, int32_t D, const int64_t* q_strides,
                                     const int64_t* k_strides, const int64_t* v_strides, float scale, void* workspace,
                                     size_t workspace_bytes, void* stream);
+
+/* The two entry points above on 16-bit elements (asr.py:262: compute_type="float16" covers the
+ * decoder's key / value caches and the cross-attention keys and values): q, k and v hold fp16
+ * (dtype WX_DTYPE_F16) or bf16 (WX_DTYPE_BF16) elements, o [B][H][64] (grouped: [B][G][H][64]) is
+ * contiguous in the same type.  The layouts and the stride arrays are those above, in elements;
+ * the alignment rule is wx_attention_h16's: every stride a multiple of 8 elements and every data
+ * pointer 16-byte aligned.  A batch stride of 0 (K / V shared by the batch) is legal, as above.
+ * Rows j >= L are never read.  The workspace is the fp32 entry points':
+ * wx_decode_attention_workspace_bytes(B, H, L) / wx_decode_attention_grouped_workspace_bytes(B, G,
+ * H, L) bytes, since the chunks' partial results stay fp32.
+ * Arithmetic: every element is widened to fp32 exactly, the chunking, every expression and every
+ * summation order are wx_decode_attention_f32's (no packed 16-bit math, no dot instruction, no
+ * fused multiply-add), the division is fp32 and the quotient is rounded to nearest even once, on
+ * the store.  So o is bit-identical to wx_decode_attention_f32 on the widened inputs, rounded to
+ * the type; the grouped entry point has the bits of the ungrouped one for every query, and row
+ * (b, h) is bit-identical whatever the batch is.
+ * B < 0, H < 1, L < 1, D != 64, a dtype that is neither, G outside 1..8: WX_E_INVALID; then B == 0:
+ * WX_OK; a null or misaligned pointer, a stride that is no multiple of 8, B or H above 65535 (grid
+ * dimensions): WX_E_INVALID; a short workspace: WX_E_WORKSPACE; all before anything is enqueued. */
+int wx_decode_attention_h16(const void* q, const void* k, const void* v, void* o, int32_t B, int32_t H, int32_t L,
+                            int32_t D, const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                            float scale, int32_t dtype, void* workspace, size_t workspace_bytes, void* stream);
+int wx_decode_attention_h16_grouped(const void* q, const void* k, const void* v, void* o, int32_t B, int32_t G,
+                                    int32_t H, int32_t L, int32_t D, const int64_t* q_strides,
+                                    const int64_t* k_strides, const int64_t* v_strides, float scale, int32_t dtype,
+                                    void* workspace, size_t workspace_bytes, void* stream);
 
 /* One beam-search selection step (WhisperDecoder.beam_search): B chunks of G beams, row r = b G + g
  * of logits (V fp32 columns at logits + r row_stride; nothing at columns >= V is read) and cum[r],

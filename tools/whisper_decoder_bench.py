@@ -30,6 +30,16 @@ positions, 1500 encoder positions:
     selection (the same host walk and cache reorder).  Where the replicated tensors do not fit, the
     baseline's chunk count is halved until they do, and the record says what it was.
 
+(d) --dtype float16 | bfloat16 (its own record, profiles/whisper_decoder_half[_bf16]_<host>.json): the
+    half route.  wx_decode_attention_h16 at B = 16, L = 1500 (cross layout) and L = 224 (cache
+    layout) against wx_decode_attention_f32 on fp32 tensors of the same shapes in the same run and
+    against torch's attention in dtype on the h16 arm's views, by (a)'s ring method, each arm's
+    ring sized by its own bytes; the grouped launch at G in {5, 8} against the ungrouped one on a
+    replica; one `step`, `generate` and `beam_search` (--beams) of WhisperDecoder(dtype=...) against
+    WhisperDecoder in fp32 in the same run and against a greedy loop over transformers' decoder cast
+    to dtype; and torch.cuda.max_memory_allocated of decoder + state for 16 chunks x --beams beams
+    in both dtypes.  No graphs are captured.
+
 Prints one JSON line; --out writes it to a file (profiles/whisper_decoder_<host>.json).
 """
 from __future__ import annotations
@@ -263,8 +273,212 @@ def beam_arm(name, g, args, torch, _lib, dev):
     return r
 
 
+def _rates(arm, nbytes):
+    arm["kv_bytes"] = nbytes
+    arm["kv_bytes_per_s"] = nbytes / arm["median_s"]
+    arm["share_of_hbm_peak"] = arm["kv_bytes_per_s"] / HBM_PEAK_BYTES_PER_S
+
+
+def half_attention_rows(D, dtype, args, torch, F, _lib, dev, B=CHUNKS):
+    """(d): wx_decode_attention_h16 against wx_decode_attention_f32 on fp32 tensors of the same shapes
+    and against torch's attention in dtype on the h16 arm's views, by (a)'s ring method; every arm's
+    ring is sized by its own key / value bytes."""
+    H = D // 64
+    rows = []
+    for L, layout in ((1500, "cross [B, L, 2D] halves"), (224, "cache [B, H, 448, 64]")):
+        def buffers(dt, nbytes):
+            ring = max(2, min(32, -(-args.ring_bytes // nbytes)))
+            kv = []
+            for _ in range(ring):
+                if L == 1500:
+                    t = torch.randn((B, L, 2 * D), device=dev).to(dt)
+                    kv.append(tuple(t[:, :, j * D:(j + 1) * D].view(B, L, H, 64).transpose(1, 2) for j in range(2)))
+                else:
+                    kv.append(tuple(torch.randn((B, H, T, 64), device=dev).to(dt) for _ in range(2)))
+            return ring, kv
+
+        n16 = 2 * B * H * L * 64 * 2
+        q32 = torch.randn((B, H, 64), device=dev)
+        q16 = q32.to(dtype)
+        out16, out32 = torch.empty((B, H, 64), dtype=dtype, device=dev), torch.empty((B, H, 64), device=dev)
+        ring16, kv16 = buffers(dtype, n16)
+
+        def h16(i):
+            k, v = kv16[i % ring16]
+            return _lib.decode_attention_h16(q16, k, v, 0.125, L=L, out=out16)
+
+        def sdpa(i):
+            k, v = kv16[i % ring16]
+            return F.scaled_dot_product_attention(q16.unsqueeze(2), k[:, :, :L], v[:, :, :L], scale=0.125)
+
+        with torch.inference_mode():
+            k0, v0 = kv16[0]
+            same = bool(torch.equal(h16(0), _lib.decode_attention_f32(q16.float(), k0.float(), v0.float(), 0.125, L=L).to(dtype)))
+            r = {"L": L, "B": B, "H": H, "layout": layout, "ring_buffers_h16": ring16,
+                 "bit_equal_f32_kernel_rounded": same,
+                 "max_abs_diff_h16_vs_sdpa": float((h16(0).float() - sdpa(0).squeeze(2).float()).abs().max()),
+                 "h16": event_timed(h16, args.repeat, args.warmup, args.steps, torch),
+                 "sdpa_dtype": event_timed(sdpa, args.repeat, args.warmup, args.steps, torch)}
+        del kv16, k0, v0
+        torch.cuda.empty_cache()
+        ring32, kv32 = buffers(torch.float32, 2 * n16)
+
+        def f32(i):
+            k, v = kv32[i % ring32]
+            return _lib.decode_attention_f32(q32, k, v, 0.125, L=L, out=out32)
+
+        with torch.inference_mode():
+            r["f32"] = event_timed(f32, args.repeat, args.warmup, args.steps, torch)
+        r["ring_buffers_f32"] = ring32
+        _rates(r["h16"], n16)
+        _rates(r["sdpa_dtype"], n16)
+        _rates(r["f32"], 2 * n16)
+        r["h16_vs_f32"] = beats(r["h16"], r["f32"])
+        r["h16_vs_sdpa_dtype"] = beats(r["h16"], r["sdpa_dtype"])
+        # outside the spreads: the slower arm's fastest repetition is slower than the faster arm's slowest
+        r["h16_faster_than_f32_outside_the_spreads"] = bool(r["h16"]["max_s"] < r["f32"]["min_s"])
+        rows.append(r)
+        del kv32
+        torch.cuda.empty_cache()
+    return rows
+
+
+def half_grouped_rows(D, dtype, args, torch, _lib, dev, B=CHUNKS, L=P):
+    """(d): wx_decode_attention_h16_grouped at G in {5, 8} against the ungrouped h16 launch at B G rows
+    on K / V replicated G times."""
+    H = D // 64
+
+    def halves(t):
+        return tuple(t[:, :, j * D:(j + 1) * D].view(t.shape[0], L, H, 64).transpose(1, 2) for j in range(2))
+
+    rows = []
+    for G in (5, 8):
+        nbytes = 2 * B * H * L * 64 * 2
+        ring = max(2, min(32, -(-args.ring_bytes // (nbytes * G))))
+        q = torch.randn((B, G, H, 64), device=dev).to(dtype)
+        shared = [torch.randn((B, L, 2 * D), device=dev).to(dtype) for _ in range(ring)]
+        out = torch.empty((B, G, H, 64), dtype=dtype, device=dev)
+
+        def grouped(i):
+            k, v = halves(shared[i % ring])
+            return _lib.decode_attention_h16_grouped(q, k, v, 0.125, out=out)
+
+        with torch.inference_mode():
+            r = {"L": L, "B": B, "G": G, "H": H, "kv_bytes_shared": nbytes, "kv_bytes_replicated": nbytes * G,
+                 "ring_buffers": ring, "grouped": event_timed(grouped, args.repeat, args.warmup, args.steps, torch)}
+        del shared
+        torch.cuda.empty_cache()
+        replicated = [torch.randn((B * G, L, 2 * D), device=dev).to(dtype) for _ in range(ring)]
+        qr, outr = q.view(B * G, H, 64), torch.empty((B * G, H, 64), dtype=dtype, device=dev)
+
+        def ungrouped_bg(i):
+            k, v = halves(replicated[i % ring])
+            return _lib.decode_attention_h16(qr, k, v, 0.125, out=outr)
+
+        with torch.inference_mode():
+            r["ungrouped_BG_rows_replicated"] = event_timed(ungrouped_bg, args.repeat, args.warmup, args.steps, torch)
+        _rates(r["grouped"], nbytes)
+        r["grouped_vs_ungrouped_BG_rows"] = beats(r["grouped"], r["ungrouped_BG_rows_replicated"])
+        rows.append(r)
+        del replicated
+        torch.cuda.empty_cache()
+    return rows
+
+
+def half_arm(name, g, dtype, args, torch, F, _lib, dev):
+    """(d) for one geometry: the launches, then the decoder in dtype against the fp32 route in the
+    same run and against transformers' decoder cast to dtype, and the peak memory of decoder + state."""
+    from transformers import WhisperConfig, WhisperForConditionalGeneration
+
+    from whisperx_amd import WhisperDecoder
+
+    D, G = g["D"], args.beams
+    sync = torch.cuda.synchronize
+    eot = V - 1
+    r = {"shape": {**g, "heads": D // 64, "vocab": V, "max_target_positions": T, "encoder_positions": P}}
+    r["attention"] = half_attention_rows(D, dtype, args, torch, F, _lib, dev)
+    r["grouped_attention"] = half_grouped_rows(D, dtype, args, torch, _lib, dev)
+    print(f"{name}: launches timed", file=sys.stderr, flush=True)
+    cfg = WhisperConfig(d_model=D, encoder_layers=1, encoder_attention_heads=1, encoder_ffn_dim=64, num_mel_bins=80,
+                        max_source_positions=P, decoder_layers=g["layers"], decoder_attention_heads=D // 64,
+                        decoder_ffn_dim=4 * D, vocab_size=V, max_target_positions=T, pad_token_id=0, bos_token_id=1,
+                        eos_token_id=2, decoder_start_token_id=1)
+    hf = WhisperForConditionalGeneration(cfg).eval().model.decoder
+    for p in hf.parameters():
+        p.requires_grad_(False)
+    enc = torch.randn((CHUNKS, P, D), device=dev)
+    prompt = torch.tensor([PROMPT] * CHUNKS, device=dev)
+    tok = torch.full((CHUNKS,), 7, dtype=torch.int64, device=dev)
+    r["memory"], decs = {}, {}
+    for dt in (torch.float32, dtype):  # decoder + the state of CHUNKS x G beams, from an empty allocator
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats(dev)
+        base = torch.cuda.memory_allocated(dev)
+        d = WhisperDecoder(hf, device=dev, dtype=dt)
+        st = d.start(enc, beams=G)
+        d.step(st, torch.full((CHUNKS * G,), 7, dtype=torch.int64, device=dev))
+        sync()
+        r["memory"][str(dt).replace("torch.", "")] = {
+            "chunks": CHUNKS, "beams": G, "allocated_bytes": torch.cuda.memory_allocated(dev) - base,
+            "max_memory_allocated_bytes": torch.cuda.max_memory_allocated(dev) - base}
+        del st
+        decs[dt] = d
+    r["memory"]["half_over_float32_allocated"] = (r["memory"][str(dtype).replace("torch.", "")]["allocated_bytes"]
+                                                  / r["memory"]["float32"]["allocated_bytes"])
+    hf = hf.to(device=dev, dtype=dtype)
+    print(f"{name}: decoders built", file=sys.stderr, flush=True)
+
+    def hf_generate():
+        with torch.inference_mode():
+            o = hf(input_ids=prompt, encoder_hidden_states=enc.to(dtype), use_cache=True)
+            steps = []
+            for _ in range(N_TOKENS):
+                lg = F.linear(o.last_hidden_state[:, -1], hf.embed_tokens.weight)
+                lg[:, eot] = float("-inf")
+                nxt = lg.argmax(-1)
+                steps.append(nxt)
+                if bool((nxt == eot).all()):
+                    break
+                if len(steps) < N_TOKENS:
+                    o = hf(input_ids=nxt[:, None], encoder_hidden_states=enc.to(dtype), past_key_values=o.past_key_values,
+                           use_cache=True)
+            return torch.stack(steps, 1)
+
+    kw = dict(max_length=len(PROMPT) + N_TOKENS, suppress_tokens=[eot])
+    for label, d in (("half", decs[dtype]), ("float32", decs[torch.float32])):
+        e = {"generated_tokens": len(d.generate(enc, PROMPT, eot, **kw)[0]),
+             "generate": timed(lambda: d.generate(enc, PROMPT, eot, **kw), args.repeat, args.warmup, sync),
+             "beam_search": timed(lambda: d.beam_search(enc, PROMPT, eot, beam_size=G, **kw), args.repeat, args.warmup, sync)}
+        st = d.start(enc)
+        for _ in range(STEP_POS):
+            d.step(st, tok)
+
+        def step(i):
+            st.pos = STEP_POS
+            return d._step(st, tok)
+
+        with torch.inference_mode():
+            e["step"] = event_timed(step, args.repeat, args.warmup, args.steps, torch)
+        e["step"]["rows"], e["step"]["position"] = CHUNKS, STEP_POS
+        r[label] = e
+        del st
+        torch.cuda.empty_cache()
+        print(f"{name}: {label} route timed", file=sys.stderr, flush=True)
+    r["beams"] = G
+    r["hf_cast_generate"] = timed(hf_generate, args.repeat, args.warmup, sync)
+    r["hf_cast_step_from_generate"] = {k: v / N_TOKENS for k, v in r["hf_cast_generate"].items() if k.endswith("_s")}
+    for what in ("generate", "beam_search", "step"):
+        r[f"{what}_half_vs_float32"] = beats(r["half"][what], r["float32"][what])
+    r["generate_half_vs_hf_cast"] = beats(r["half"]["generate"], r["hf_cast_generate"])
+    del hf, decs, enc
+    torch.cuda.empty_cache()
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--dtype", default="float32", choices=["float32", "float16", "bfloat16"],
+                    help="float16 / bfloat16: (d), the half route's record (profiles/whisper_decoder_half*_<host>.json)")
     ap.add_argument("--arms", default="decoder", choices=["decoder", "beam"], help="(a) and (b), or (c)")
     ap.add_argument("--beams", type=int, default=5)
     ap.add_argument("--geometries", default="base,large-v2")
@@ -289,8 +503,14 @@ def main():
               "lib": os.path.basename(_lib.LIB_PATH), "dtype": "float32", "decode_chunk": _lib.DECODE_CHUNK,
               "peaks": {"hbm_bytes_per_s": HBM_PEAK_BYTES_PER_S}, "geometries": {}}
     eot = V - 1  # suppressed: both greedy loops run their full length
+    if args.dtype != "float32":
+        result["dtype"] = args.dtype
     for name in args.geometries.split(","):
         g = GEOMETRIES[name]
+        if args.dtype != "float32":
+            torch.manual_seed(args.seed)
+            result["geometries"][name] = half_arm(name, g, getattr(torch, args.dtype), args, torch, F, _lib, dev)
+            continue
         if args.arms == "beam":
             torch.manual_seed(args.seed)
             result["geometries"][name] = beam_arm(name, g, args, torch, _lib, dev)

@@ -26,7 +26,7 @@ SRC_PATHS = [SRC_PATH, os.path.join(_HERE, "csrc", "wx_binarize.hip"), os.path.j
              os.path.join(_HERE, "csrc", "wx_vad.hip"), os.path.join(_HERE, "csrc", "wx_diarize.hip"),
              os.path.join(_HERE, "csrc", "wx_mel.hip"), os.path.join(_HERE, "csrc", "wx_whisper.hip"),
              os.path.join(_HERE, "csrc", "wx_decode.hip"), os.path.join(_HERE, "csrc", "wx_beam.hip"),
-             os.path.join(_HERE, "csrc", "wx_attention_h16.hip")]
+             os.path.join(_HERE, "csrc", "wx_attention_h16.hip"), os.path.join(_HERE, "csrc", "wx_decode_h16.hip")]
 INST_PATH = os.path.join(_HERE, "csrc", "wx_align_inst.hip")
 HDR_PATHS = sorted(glob.glob(os.path.join(_HERE, "csrc", "*.h"))) + [INST_PATH]  # (a new header: a rebuild)
 INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
@@ -116,6 +116,10 @@ SIGNATURES = {
     "wx_beam_topk": (ctypes.c_int, [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "wx_attention_h16": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _i32, _vp]),
     "wx_add_layernorm_h16": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _f32, _i32, _vp, _vp, _vp]),
+    "wx_decode_attention_h16": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _i32, _vp,
+                                               _sz, _vp]),
+    "wx_decode_attention_h16_grouped": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32,
+                                                       _i32, _vp, _sz, _vp]),
 }
 
 
@@ -1040,6 +1044,67 @@ def add_layernorm_h16(a: torch.Tensor, b: Optional[torch.Tensor], gamma: torch.T
                                         int(b2.stride(0)) if rows and b2 is not None else D, _ptr(gamma), _ptr(beta),
                                         float(eps), code, _ptr(y), _ptr(s), _stream(a.device)))
     return (y, s) if want_sum else y
+
+
+def _decode_attention_h16(who: str, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, L: Optional[int],
+                          out: Optional[torch.Tensor], grouped: bool) -> torch.Tensor:
+    """decode_attention_h16 (q [B, H, 64]) and decode_attention_h16_grouped (q [B, G, H, 64])."""
+    lib = load()
+    qd = 4 if grouped else 3
+    lead = "[B, G, H, 64]" if grouped else "[B, H, 64]"
+    if q.dim() != qd or k.dim() != 4 or v.dim() != 4:
+        raise WXError(f"{who}: q {tuple(q.shape)} / k {tuple(k.shape)} / v {tuple(v.shape)} are not "
+                      f"{lead} / [B, H, Lcap, 64] / [B, H, Lcap, 64]")
+    B, H, D = int(q.shape[0]), int(q.shape[-2]), int(q.shape[-1])
+    Lcap = int(k.shape[2])
+    L = Lcap if L is None else int(L)
+    if tuple(k.shape) != (B, H, Lcap, D) or tuple(v.shape) != (B, H, Lcap, D) or not 1 <= L <= Lcap:
+        raise WXError(f"{who}: k {tuple(k.shape)} / v {tuple(v.shape)} do not hold {L} rows for q {tuple(q.shape)}")
+    dev = q.device
+    code = HALF_DTYPES.get(q.dtype)
+    for t in (q, k, v):
+        if code is None or t.dtype != q.dtype or not t.is_cuda or t.device != dev or t.stride(-1) != 1:
+            raise WXError(f"{who}: q, k and v must share one of float16 / bfloat16, on one HIP device with a contiguous "
+                          "head dim")
+    if out is None:
+        out = torch.empty(tuple(q.shape), dtype=q.dtype, device=dev)
+    if tuple(out.shape) != tuple(q.shape) or out.dtype != q.dtype or out.device != dev or not out.is_contiguous():
+        raise WXError(f"{who}: out must be a contiguous {lead} tensor of the queries' dtype on their device")
+    st = [(ctypes.c_int64 * n)(*(int(x) for x in t.stride()[:n])) for t, n in ((q, qd - 1), (k, 3), (v, 3))]
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        if grouped:
+            G = int(q.shape[1])
+            ws = _scratch.get("decode_attention_grouped", dev, lib.wx_decode_attention_grouped_workspace_bytes(B, G, H, L),
+                              stream)
+            _check(lib.wx_decode_attention_h16_grouped(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, G, H, L, D, st[0], st[1],
+                                                       st[2], float(scale), code, _ptr(ws), ws.numel(),
+                                                       ctypes.c_void_p(stream.cuda_stream)))
+        else:
+            ws = _scratch.get("decode_attention", dev, lib.wx_decode_attention_workspace_bytes(B, H, L), stream)
+            _check(lib.wx_decode_attention_h16(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, H, L, D, st[0], st[1], st[2],
+                                               float(scale), code, _ptr(ws), ws.numel(),
+                                               ctypes.c_void_p(stream.cuda_stream)))
+    return out
+
+
+def decode_attention_h16(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, L: Optional[int] = None,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """wx_decode_attention_h16: decode_attention_f32 on fp16 or bf16 device views of one dtype: q
+    [B, H, 64] against rows 0 .. L - 1 of k / v [B, H, Lcap, 64], read in place (head dim contiguous,
+    every other stride a multiple of 8 elements, 16-byte aligned).  Returns [B, H, 64] contiguous in
+    that dtype (`out` when given) on the current stream: decode_attention_f32 of the widened inputs,
+    rounded once."""
+    return _decode_attention_h16("decode_attention_h16", q, k, v, scale, L, out, False)
+
+
+def decode_attention_h16_grouped(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float,
+                                 L: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """wx_decode_attention_h16_grouped: G query rows per (batch, head), q [B, G, H, 64] fp16 or bf16,
+    against the k / v [B, H, Lcap, 64] they share, under decode_attention_h16's rules.  Returns
+    [B, G, H, 64] contiguous in that dtype; row (b, g, h) has the bits decode_attention_h16 gives that
+    query on the same k / v."""
+    return _decode_attention_h16("decode_attention_h16_grouped", q, k, v, scale, L, out, True)
 
 
 class PackedSegments:

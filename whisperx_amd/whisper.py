@@ -39,6 +39,18 @@ search the G beams of a chunk are rows b G + g of the state; their cross-attenti
 one K_x / V_x (wx_decode_attention_f32_grouped), and the 2G best continuations of every chunk come
 from wx_beam_topk.  Temperature fallback, timestamps and the tokenizer are not built.
 
+With `dtype` float16 or bfloat16 the decoder runs the reference's compute type too (asr.py:262).
+Rounded to dtype: the GEMMs (weights and biases once, at construction; q/k/v, out, fc1, fc2 and the
+cross-attention k/v GEMM of start()), the GELU, both attentions with the self-attention caches and
+the cross-attention keys and values they read (wx_decode_attention_h16, and
+wx_decode_attention_h16_grouped for a chunk's beams), the token embedding (kept only as its dtype
+copy: the lookup is float(embed[id]) + pos, the output projection a dtype GEMM) and so the logits,
+which are the dtype GEMM's output widened to fp32.  Not rounded: the residual stream, every
+LayerNorm (computed in fp32, its output rounded once: wx_add_layernorm_h16), the positional table,
+the softmax statistics of the attention kernels (fp32 maxima, sums and accumulators; one rounding
+on the store) and everything after the logits: the log-probabilities, the running sums and the
+selection of beam search (wx_beam_topk on the fp32 logits).
+
 Without a GPU the same arithmetic runs in torch ops on the host (`F.conv1d`, `F.layer_norm`,
 `F.scaled_dot_product_attention`).  Both halves read their weights through one loader (`_Half`,
 `_Taker`) and run their layers as stages of one residual chain (`_chain`) on either route.
@@ -420,7 +432,7 @@ class DecoderState:
     `stages`: the decoder's layers bound to these tensors, built at the first step.  With `G` > 1
     beams per chunk (`start(beams=G)`) there are `rows` = B G sequences, row b G + g beam g of chunk
     b: the caches are [B G, H, max_target_positions, 64] and `cross` stays [B, P, 2D], shared by a
-    chunk's beams."""
+    chunk's beams.  `cross` and the caches have the decoder's dtype."""
 
     def __init__(self, B: int, P: int, cross, self_k, self_v, kernels: bool, beams: int = 1):
         self.B, self.P, self.pos = B, P, 0
@@ -442,11 +454,24 @@ class WhisperDecoder:
     projection is the token embedding (tied, as in both sources); a `proj_out.weight` is accepted
     only if it equals the embedding.  The derived weights ([Wq; Wk; Wv] with a zero bias block for
     k, [Wk_x; Wv_x]) are built once here; the caller's module is read, never patched.  `device`:
-    where the weights go (default: the current HIP device when one is visible, else the CPU)."""
+    where the weights go (default: the current HIP device when one is visible, else the CPU).
+    `dtype`: float32 (the default: the fp32 code path, unchanged), or float16 / bfloat16 for the half
+    route of the module's docstring.  The Linear layers' weights and biases and the token embedding
+    are rounded to it here (a rounding that is not finite is a ValueError naming the tensor; the
+    `proj_out.weight` check runs on the fp32 tensors first) and only those copies are kept; the
+    positional table and the LayerNorm parameters stay fp32.  The state then holds the
+    cross-attention keys and values and the self-attention caches in dtype, half the bytes.  The
+    GEMMs, the GELU, the attention, the embedding and the logits are rounded; the residual stream,
+    the norms, the positional table, the softmax statistics and the log-probabilities are not.
+    `step` and `logits` return fp32 either way, and `generate`, `beam_search`, `reorder` and
+    `detect_language` are the same algorithms."""
 
-    def __init__(self, weights, device=None):
-        self.device = _device(device)
-        take = _Taker(_state_dict(weights, _DECODER), self.device, "WhisperDecoder")
+    def __init__(self, weights, device=None, dtype: torch.dtype = torch.float32):
+        if dtype not in _DTYPES:
+            raise ValueError(f"WhisperDecoder: dtype must be torch.float32, torch.float16 or torch.bfloat16, got {dtype!r}")
+        self.device, self.dtype = _device(device), dtype
+        half = dtype != torch.float32
+        take = _Taker(_state_dict(weights, _DECODER), self.device, "WhisperDecoder", dtype if half else None)
         self.embed = take("embed_tokens.weight")
         if self.embed.dim() != 2:
             raise ValueError(f"WhisperDecoder: tensor 'embed_tokens.weight' has shape {tuple(self.embed.shape)}, expected [V, D]")
@@ -458,6 +483,8 @@ class WhisperDecoder:
         if take.sd.get("proj_out.weight") is not None and not torch.equal(take("proj_out.weight", (V, D)), self.embed):
             raise ValueError("WhisperDecoder: tensor 'proj_out.weight' differs from embed_tokens.weight; the output "
                              "projection must be tied to the token embedding")
+        if half:  # only the rounded copy stays: the lookup and the output projection read it
+            self.embed = take.gemm("embed_tokens.weight")
         self.pos = take.table("embed_positions.weight", "T", D)
         self.max_target_positions = int(self.pos.shape[0])
         self.layers = []
@@ -495,13 +522,13 @@ class WhisperDecoder:
         kernels = self.device.type == "cuda" if kernels is None else bool(kernels)
         if kernels and self.device.type != "cuda":
             raise ValueError("WhisperDecoder.start: the HIP route needs the decoder on a HIP device")
-        x = x.to(device=self.device, dtype=torch.float32)
+        x = x.to(device=self.device, dtype=self.dtype)
         B, P = int(x.shape[0]), int(x.shape[1])
         with self._ctx():
             cross = [F.linear(x, *L["kv_x"]) for L in self.layers]
             shape = (B * beams, self.H, self.max_target_positions, 64)
-            self_k = [torch.zeros(shape, dtype=torch.float32, device=self.device) for _ in self.layers]
-            self_v = [torch.zeros(shape, dtype=torch.float32, device=self.device) for _ in self.layers]
+            self_k = [torch.zeros(shape, dtype=self.dtype, device=self.device) for _ in self.layers]
+            self_v = [torch.zeros(shape, dtype=self.dtype, device=self.device) for _ in self.layers]
         return DecoderState(B, P, cross, self_k, self_v, kernels, beams)
 
     def _tokens(self, tokens, shape, who: str) -> torch.Tensor:
@@ -529,6 +556,11 @@ class WhisperDecoder:
         if st.stages is None:  # once per state: the step path only calls them
             st.stages = self._stages(weakref.proxy(st))  # (a proxy: the state owns its stages, not they it)
         with self._ctx():
+            if self.dtype != torch.float32:
+                h = F.embedding(tok, self.embed).float() + self.pos[st.pos]
+                y = _chain_half(h, st.stages, self.ln_f, self.dtype, st.kernels)
+                st.pos += 1
+                return F.linear(y.to(self.dtype), self.embed).float()
             h = F.embedding(tok, self.embed) + self.pos[st.pos]
             y = _chain(h, st.stages, self.ln_f, _lib.add_layernorm if st.kernels else None)
             st.pos += 1
@@ -539,14 +571,20 @@ class WhisperDecoder:
         state is at when they are called: both attentions on wx_decode_attention_f32 or on
         torch's; the first writes the cache rows.  A state of G > 1 beams runs the self-attention
         over its R = B G rows and the cross-attention of a chunk's G beams on the chunk's one
-        K / V: wx_decode_attention_f32_grouped, or torch's on a view expanded over the beams."""
+        K / V: wx_decode_attention_f32_grouped, or torch's on a view expanded over the beams.  A
+        float16 / bfloat16 decoder takes wx_decode_attention_h16 and its grouped form, or torch's
+        attention in that dtype, on the dtype tensors of the state."""
         B, G, R, P, D, H = st.B, st.G, st.rows, st.P, self.D, self.H
         if st.kernels:
+            half = self.dtype != torch.float32
+            one = _lib.decode_attention_h16 if half else _lib.decode_attention_f32
+            grouped = _lib.decode_attention_h16_grouped if half else _lib.decode_attention_f32_grouped
+
             def attend(q, k, v, n=None):
-                return _lib.decode_attention_f32(q, k, v, 0.125, L=n).view(R, D)
+                return one(q, k, v, 0.125, L=n).view(R, D)
 
             def attend_beams(q, k, v):
-                return _lib.decode_attention_f32_grouped(q.view(B, G, H, 64), k, v, 0.125).view(R, D)
+                return grouped(q.view(B, G, H, 64), k, v, 0.125).view(R, D)
         else:
             def attend(q, k, v, n=None):
                 return F.scaled_dot_product_attention(q.unsqueeze(2), k[:, :, :n], v[:, :, :n], scale=0.125).reshape(R, D)
@@ -796,7 +834,7 @@ class WhisperDecoder:
         return torch.softmax(lg[:, torch.tensor(ids, dtype=torch.int64, device=self.device)], -1)
 
 
-def load_whisper_decoder(path: str, device=None) -> WhisperDecoder:
+def load_whisper_decoder(path: str, device=None, dtype: torch.dtype = torch.float32) -> WhisperDecoder:
     """A WhisperDecoder from a state-dict file (as load_whisper_encoder reads it).  The file may
-    hold a whole model; only the decoder's tensors are used."""
-    return WhisperDecoder(_load_state_dict(path, "load_whisper_decoder"), device=device)
+    hold a whole model; only the decoder's tensors are used.  `dtype`: WhisperDecoder's."""
+    return WhisperDecoder(_load_state_dict(path, "load_whisper_decoder"), device=device, dtype=dtype)
