@@ -42,6 +42,10 @@
  *   wx_decode_attention_h16, wx_decode_attention_h16_grouped <- whisperx/asr.py:262
  *                        compute_type="float16" on the decoder (the two decode-step attentions
  *                        on fp16 / bf16 caches and cross-attention keys / values)
+ *   wx_prefill_attention_f32, wx_prefill_attention_h16 <- whisperx/asr.py:35-45  initial_prompt /
+ *                        prefix (the prompt of a batch in one forward: n queries per sequence and
+ *                        head against the cache under a causal mask, and against the
+ *                        cross-attention keys / values)
  *
  * Conventions
  *   - All data pointers are DEVICE pointers (allocated by the caller; the library never
@@ -565,6 +569,43 @@ int wx_decode_attention_h16_grouped(const void* q, const void* k, const void* v,
                                     int32_t H, int32_t L, int32_t D, const int64_t* q_strides,
                                     const int64_t* k_strides, const int64_t* v_strides, float scale, int32_t dtype,
                                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* Attention of a prompt prefill (WhisperDecoder.prefill): Tq queries per (batch, head) against Tk
+ * key / value rows, under a causal mask or without one,
+ *     o[b][i][h][:] = sum_j softmax_j(scale * q[b][h][i][:] . k[b][h][j][:]) v[b][h][j][:]
+ *         over j in [0, Tk)                        when causal < 0,
+ *         over j in [0, min(Tk, causal + i + 1))   when causal >= 0 (query i sits at position causal + i).
+ *   q: [B][H][Tq][64] view, row (b, h, i) at q + b q_strides[0] + h q_strides[1] + i q_strides[2]
+ *      (the q slice of a fused [B][n][3 H 64] GEMM output as it is); k, v: [B][H][Tk][64] views by
+ *      {batch, head, time} element strides, read in place: the self-attention cache
+ *      [R][H][max_target_positions][64] (or every G-th row of it: any batch stride is legal, 0 too)
+ *      and the two halves of the cross-attention [B][P][2 H 64] tensor.  The head dim is contiguous.
+ *      o: [B][Tq][H][64] contiguous.  No workspace.
+ *   f32: every stride a multiple of 4 floats, every pointer 16-byte aligned (wx_decode_attention_f32's
+ *      rule).  h16: fp16 (WX_DTYPE_F16) or bf16 (WX_DTYPE_BF16) elements, o in the same type; every
+ *      stride a multiple of 8 elements, every pointer 16-byte aligned (wx_decode_attention_h16's
+ *      rule).  Both: the time strides of k and v lie in [0, 2^23] (a key tile is addressed by
+ *      32-bit byte offsets).
+ * One workgroup per (batch, head, 32-query tile), 4 waves over every 4th 32-key tile on
+ * v_mfma_f32_32x32x2f32 with the online softmax in fp32, merged through LDS in wave order
+ * (wx_attention_f32's arithmetic).  Key tiles are aligned to key 0 and a wave takes the same tiles
+ * in the same order whatever the launch is; a key masked for a row contributes exactly 0 and leaves
+ * the row's running maximum alone; key tiles wholly above a query tile's diagonal are skipped.  So
+ * row (b, i, h) depends only on its query, on causal + i and on K / V rows 0 .. causal + i (0 ..
+ * Tk - 1 without a mask): it is bit-identical whatever B, Tq and the rest of Tk are and however
+ * causal + i splits into its two terms.  K / V rows at and past min(Tk, causal + Tq) are never read.
+ * h16: every element is widened to fp32 exactly, every expression is the f32 kernel's (no packed
+ * 16-bit math, no 16-bit MFMA) and the quotient is rounded to nearest even once, on the store: o is
+ * bit-identical to wx_prefill_attention_f32 on the widened inputs, rounded to the type.
+ * B < 0, H < 1, Tq < 1, Tk < 1, D != 64 or an unknown dtype: WX_E_INVALID; then B == 0: WX_OK; then a
+ * null or misaligned pointer, a bad stride or more than 2^31 - 1 workgroups: WX_E_INVALID; all
+ * before anything is enqueued. */
+int wx_prefill_attention_f32(const float* q, const float* k, const float* v, float* o, int32_t B, int32_t H,
+                             int32_t Tq, int32_t Tk, int32_t causal, int32_t D, const int64_t* q_strides,
+                             const int64_t* k_strides, const int64_t* v_strides, float scale, void* stream);
+int wx_prefill_attention_h16(const void* q, const void* k, const void* v, void* o, int32_t B, int32_t H, int32_t Tq,
+                             int32_t Tk, int32_t causal, int32_t D, const int64_t* q_strides, const int64_t* k_strides,
+                             const int64_t* v_strides, float scale, int32_t dtype, void* stream);
 
 /* One beam-search selection step (WhisperDecoder.beam_search): B chunks of G beams, row r = b G + g
  * of logits (V fp32 columns at logits + r row_stride; nothing at columns >= V is read) and cum[r],

@@ -40,6 +40,17 @@ positions, 1500 encoder positions:
     to dtype; and torch.cuda.max_memory_allocated of decoder + state for 16 chunks x --beams beams
     in both dtypes.  No graphs are captured.
 
+(e) --arms prefill (its own record, profiles/whisper_prefill_<host>.json): the prompt prefill, fp32
+    and the half type (--dtype, float16 by default) in the same run.  One wx_prefill_attention_f32 /
+    _h16 launch against F.scaled_dot_product_attention with the same boolean mask on the same views,
+    B = 16: causal at Tq = Tk in {4, 224} on the cache layout with q the slice of a fused
+    [B, Tq, 3D] tensor, and without a mask at Tq in {4, 224} x Tk = 1500 on the cross layout, by
+    (a)'s ring method; with the bytes (q, the visible K / V rows, o) and the FLOP (4 x 64 per visible
+    (query, key) pair) the shapes give, and those over the time as shares of the HBM and fp32-MFMA
+    peaks (the h16 arm computes on the fp32 MFMA too).  Then `generate` (64 tokens x 16 chunks) and
+    `beam_search` (--beams) from a 4-id and from a 224-id prompt, and `logits` on [16, 64], each
+    with prefill=True against prefill=False in the same run.
+
 Prints one JSON line; --out writes it to a file (profiles/whisper_decoder_<host>.json).
 """
 from __future__ import annotations
@@ -55,6 +66,7 @@ if ROOT not in sys.path:
 from benchlib import beats, event_timed, timed  # noqa: E402
 
 HBM_PEAK_BYTES_PER_S = 8.0e12  # MI355X HBM3E, spec
+F32_MFMA_PEAK_FLOPS = 157.3e12  # MI355X v_mfma_f32_*_f32, spec
 GEOMETRIES = {"base": {"D": 512, "layers": 6}, "large-v2": {"D": 1280, "layers": 32}}
 V, T, P = 51865, 448, 1500
 PROMPT = [50258, 50259, 50359]
@@ -475,11 +487,114 @@ def half_arm(name, g, dtype, args, torch, F, _lib, dev):
     return r
 
 
+def prefill_attention_rows(D, dtype, args, torch, F, _lib, dev, B=CHUNKS):
+    """(e): one prefill attention launch against torch's attention with the same mask on the same views."""
+    H = D // 64
+    es = 4 if dtype == torch.float32 else 2
+    ours_fn = _lib.prefill_attention_f32 if dtype == torch.float32 else _lib.prefill_attention_h16
+    rows = []
+    for kind, Tq, Tk in (("causal", 4, 4), ("causal", 224, 224), ("cross", 4, P), ("cross", 224, P)):
+        pairs = sum(min(Tk, i + 1) for i in range(Tq)) if kind == "causal" else Tq * Tk  # visible (query, key) pairs
+        nbytes = B * H * 64 * es * (2 * Tq + 2 * Tk)  # q and o, the K and V rows some query sees
+        flop = 4 * 64 * B * H * pairs
+        ring = max(2, min(32, -(-args.ring_bytes // nbytes)))
+        fused = torch.randn((B, Tq, 3, H, 64), device=dev).to(dtype)
+        q = fused[:, :, 0].transpose(1, 2)  # the q slice of a fused q/k/v GEMM output, in place
+        kv = []
+        for _ in range(ring):
+            if kind == "cross":
+                t = torch.randn((B, Tk, 2 * D), device=dev).to(dtype)
+                kv.append(tuple(t[:, :, j * D:(j + 1) * D].view(B, Tk, H, 64).transpose(1, 2) for j in range(2)))
+            else:
+                kv.append(tuple(torch.randn((B, H, T, 64), device=dev).to(dtype) for _ in range(2)))
+        causal = 0 if kind == "causal" else None
+        mask = None if causal is None else torch.ones((Tq, Tk), dtype=torch.bool, device=dev).tril()
+
+        def ours(i):
+            k, v = kv[i % ring]
+            return ours_fn(q, k, v, 0.125, causal=causal, Tk=Tk)
+
+        def sdpa(i):
+            k, v = kv[i % ring]
+            return F.scaled_dot_product_attention(q, k[:, :, :Tk], v[:, :, :Tk], attn_mask=mask, scale=0.125)
+
+        with torch.inference_mode():
+            r = {"mask": kind, "Tq": Tq, "Tk": Tk, "B": B, "H": H, "ring_buffers": ring, "bytes": nbytes, "flop": flop,
+                 "layout": "cross [B, Tk, 2D] halves" if kind == "cross" else "cache [B, H, 448, 64]",
+                 "max_abs_diff_ours_vs_sdpa": float((ours(0).float() - sdpa(0).transpose(1, 2).float()).abs().max()),
+                 "ours": event_timed(ours, args.repeat, args.warmup, args.steps, torch),
+                 "sdpa": event_timed(sdpa, args.repeat, args.warmup, args.steps, torch)}
+        for arm in ("ours", "sdpa"):
+            r[arm]["bytes_per_s"] = nbytes / r[arm]["median_s"]
+            r[arm]["share_of_hbm_peak"] = r[arm]["bytes_per_s"] / HBM_PEAK_BYTES_PER_S
+            r[arm]["flop_per_s"] = flop / r[arm]["median_s"]
+        r["ours"]["share_of_f32_mfma_peak"] = r["ours"]["flop_per_s"] / F32_MFMA_PEAK_FLOPS
+        r["ours_vs_sdpa"] = beats(r["ours"], r["sdpa"])
+        r["hbm_and_mfma_time_separated"] = "not measured"
+        rows.append(r)
+        del kv
+        torch.cuda.empty_cache()
+    return rows
+
+
+def prefill_arm(name, g, half_dtype, args, torch, F, _lib, dev):
+    """(e) for one geometry: the launches, then generate / beam_search / logits with and without
+    prefill, in fp32 and in the half type."""
+    from transformers import WhisperConfig, WhisperForConditionalGeneration
+
+    from whisperx_amd import WhisperDecoder
+
+    D, G = g["D"], args.beams
+    sync = torch.cuda.synchronize
+    eot = V - 1
+    r = {"shape": {**g, "heads": D // 64, "vocab": V, "max_target_positions": T, "encoder_positions": P}, "beams": G}
+    cfg = WhisperConfig(d_model=D, encoder_layers=1, encoder_attention_heads=1, encoder_ffn_dim=64, num_mel_bins=80,
+                        max_source_positions=P, decoder_layers=g["layers"], decoder_attention_heads=D // 64,
+                        decoder_ffn_dim=4 * D, vocab_size=V, max_target_positions=T, pad_token_id=0, bos_token_id=1,
+                        eos_token_id=2, decoder_start_token_id=1)
+    hf = WhisperForConditionalGeneration(cfg).eval().model.decoder
+    for p in hf.parameters():
+        p.requires_grad_(False)
+    enc = torch.randn((CHUNKS, P, D), device=dev)
+    gen = torch.Generator().manual_seed(args.seed)
+    prompts = {4: PROMPT + [50363], 224: PROMPT + torch.randint(0, 50257, (221,), generator=gen).tolist()}
+    forced = torch.randint(0, 50257, (CHUNKS, N_TOKENS), generator=gen)
+    for dt in (torch.float32, half_dtype):
+        label = str(dt).replace("torch.", "")
+        e = {"attention": prefill_attention_rows(D, dt, args, torch, F, _lib, dev)}
+        print(f"{name} {label}: launches timed", file=sys.stderr, flush=True)
+        dec = WhisperDecoder(hf, device=dev, dtype=dt)
+        for n, prompt in prompts.items():
+            kw = dict(max_length=n + N_TOKENS, suppress_tokens=[eot])
+            row = {"prompt_ids": n, "chunks": CHUNKS, "generated_tokens": N_TOKENS}
+            for what, call in (("generate", lambda pf: dec.generate(enc, prompt, eot, prefill=pf, **kw)),
+                               ("beam_search", lambda pf: dec.beam_search(enc, prompt, eot, beam_size=G, prefill=pf, **kw))):
+                a, b = call(True), call(False)
+                ids = (lambda x: x) if what == "generate" else (lambda x: [h[0].ids for h in x])
+                row[what] = {"prefill": timed(lambda: call(True), args.repeat, args.warmup, sync),
+                             "stepwise": timed(lambda: call(False), args.repeat, args.warmup, sync),
+                             "rows_with_equal_ids": sum(x == y for x, y in zip(ids(a), ids(b))) / CHUNKS}
+                row[what]["prefill_vs_stepwise"] = beats(row[what]["prefill"], row[what]["stepwise"])
+                row[what]["saved_s_median"] = row[what]["stepwise"]["median_s"] - row[what]["prefill"]["median_s"]
+            e[f"prompt_{n}"] = row
+            print(f"{name} {label}: prompt of {n} timed", file=sys.stderr, flush=True)
+        a, b = dec.logits(enc, forced, prefill=True), dec.logits(enc, forced, prefill=False)
+        e["logits"] = {"shape": [CHUNKS, N_TOKENS], "max_abs_diff_prefill_vs_stepwise": float((a - b).abs().max()),
+                       "prefill": timed(lambda: dec.logits(enc, forced, prefill=True), args.repeat, args.warmup, sync),
+                       "stepwise": timed(lambda: dec.logits(enc, forced, prefill=False), args.repeat, args.warmup, sync)}
+        e["logits"]["prefill_vs_stepwise"] = beats(e["logits"]["prefill"], e["logits"]["stepwise"])
+        r[label] = e
+        del dec, a, b
+        torch.cuda.empty_cache()
+    del hf, enc
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", default="float32", choices=["float32", "float16", "bfloat16"],
                     help="float16 / bfloat16: (d), the half route's record (profiles/whisper_decoder_half*_<host>.json)")
-    ap.add_argument("--arms", default="decoder", choices=["decoder", "beam"], help="(a) and (b), or (c)")
+    ap.add_argument("--arms", default="decoder", choices=["decoder", "beam", "prefill"], help="(a) and (b), (c), or (e)")
     ap.add_argument("--beams", type=int, default=5)
     ap.add_argument("--geometries", default="base,large-v2")
     ap.add_argument("--repeat", type=int, default=5)
@@ -502,10 +617,18 @@ def main():
     result = {"tool": "tools/whisper_decoder_bench.py", "device": torch.cuda.get_device_name(0),
               "lib": os.path.basename(_lib.LIB_PATH), "dtype": "float32", "decode_chunk": _lib.DECODE_CHUNK,
               "peaks": {"hbm_bytes_per_s": HBM_PEAK_BYTES_PER_S}, "geometries": {}}
+    if args.arms == "prefill":
+        result["peaks"]["f32_mfma_flop_per_s"] = F32_MFMA_PEAK_FLOPS
+        half = getattr(torch, args.dtype if args.dtype != "float32" else "float16")
+        result["dtype"] = ["float32", str(half).replace("torch.", "")]
+        for name in args.geometries.split(","):
+            torch.manual_seed(args.seed)
+            result["geometries"][name] = prefill_arm(name, GEOMETRIES[name], half, args, torch, F, _lib, dev)
+        args.geometries = ""
     eot = V - 1  # suppressed: both greedy loops run their full length
     if args.dtype != "float32":
         result["dtype"] = args.dtype
-    for name in args.geometries.split(","):
+    for name in filter(None, args.geometries.split(",")):
         g = GEOMETRIES[name]
         if args.dtype != "float32":
             torch.manual_seed(args.seed)

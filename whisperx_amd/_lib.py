@@ -26,7 +26,8 @@ SRC_PATHS = [SRC_PATH, os.path.join(_HERE, "csrc", "wx_binarize.hip"), os.path.j
              os.path.join(_HERE, "csrc", "wx_vad.hip"), os.path.join(_HERE, "csrc", "wx_diarize.hip"),
              os.path.join(_HERE, "csrc", "wx_mel.hip"), os.path.join(_HERE, "csrc", "wx_whisper.hip"),
              os.path.join(_HERE, "csrc", "wx_decode.hip"), os.path.join(_HERE, "csrc", "wx_beam.hip"),
-             os.path.join(_HERE, "csrc", "wx_attention_h16.hip"), os.path.join(_HERE, "csrc", "wx_decode_h16.hip")]
+             os.path.join(_HERE, "csrc", "wx_attention_h16.hip"), os.path.join(_HERE, "csrc", "wx_decode_h16.hip"),
+             os.path.join(_HERE, "csrc", "wx_prefill.hip")]
 INST_PATH = os.path.join(_HERE, "csrc", "wx_align_inst.hip")
 HDR_PATHS = sorted(glob.glob(os.path.join(_HERE, "csrc", "*.h"))) + [INST_PATH]  # (a new header: a rebuild)
 INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
@@ -120,6 +121,10 @@ SIGNATURES = {
                                                _sz, _vp]),
     "wx_decode_attention_h16_grouped": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32,
                                                        _i32, _vp, _sz, _vp]),
+    "wx_prefill_attention_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32,
+                                                _vp]),
+    "wx_prefill_attention_h16": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32,
+                                                _i32, _vp]),
 }
 
 
@@ -1105,6 +1110,61 @@ def decode_attention_h16_grouped(q: torch.Tensor, k: torch.Tensor, v: torch.Tens
     [B, G, H, 64] contiguous in that dtype; row (b, g, h) has the bits decode_attention_h16 gives that
     query on the same k / v."""
     return _decode_attention_h16("decode_attention_h16_grouped", q, k, v, scale, L, out, True)
+
+
+def _prefill_attention(who: str, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, causal: Optional[int],
+                       Tk: Optional[int], half: bool) -> torch.Tensor:
+    """prefill_attention_f32 and prefill_attention_h16."""
+    lib = load()
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise WXError(f"{who}: q {tuple(q.shape)} / k {tuple(k.shape)} / v {tuple(v.shape)} are not "
+                      "[B, H, Tq, 64] / [B, H, Tkcap, 64] / [B, H, Tkcap, 64]")
+    B, H, Tq, D = (int(x) for x in q.shape)
+    cap = int(k.shape[2])
+    Tk = cap if Tk is None else int(Tk)
+    if tuple(k.shape) != (B, H, cap, D) or tuple(v.shape) != (B, H, cap, D) or not 1 <= Tk <= cap:
+        raise WXError(f"{who}: k {tuple(k.shape)} / v {tuple(v.shape)} do not hold {Tk} rows for q {tuple(q.shape)}")
+    causal = -1 if causal is None else int(causal)
+    if causal < 0 and causal != -1 or causal > 2 ** 31 - 1:
+        raise WXError(f"{who}: causal must be None or the position of query 0 (>= 0), got {causal}")
+    dev = q.device
+    code = HALF_DTYPES.get(q.dtype) if half else None
+    for t in (q, k, v):
+        if (code is None if half else t.dtype != torch.float32) or t.dtype != q.dtype or not t.is_cuda or \
+                t.device != dev or t.stride(-1) != 1:
+            raise WXError(f"{who}: q, k and v must {'share one of float16 / bfloat16' if half else 'be float32 tensors'}, "
+                          "on one HIP device with a contiguous head dim")
+    o = torch.empty((B, Tq, H, D), dtype=q.dtype, device=dev)
+    st = [(ctypes.c_int64 * 3)(*(int(x) for x in t.stride()[:3])) for t in (q, k, v)]
+    with torch.cuda.device(dev):
+        if half:
+            _check(lib.wx_prefill_attention_h16(_ptr(q), _ptr(k), _ptr(v), _ptr(o), B, H, Tq, Tk, causal, D, st[0], st[1],
+                                                st[2], float(scale), code, _stream(dev)))
+        else:
+            _check(lib.wx_prefill_attention_f32(_ptr(q), _ptr(k), _ptr(v), _ptr(o), B, H, Tq, Tk, causal, D, st[0], st[1],
+                                                st[2], float(scale), _stream(dev)))
+    return o
+
+
+def prefill_attention_f32(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, causal: Optional[int] = None,
+                          Tk: Optional[int] = None) -> torch.Tensor:
+    """wx_prefill_attention_f32: Tq query rows per (batch, head), q [B, H, Tq, 64], against rows
+    0 .. Tk - 1 of k / v [B, H, Tkcap, 64] (Tk defaults to Tkcap): fp32 device views of any batch /
+    head / row stride with a contiguous head dim and 16-byte aligned rows, read in place (the
+    self-attention cache or a `cache[::G]` view of it, the halves of the cross-attention
+    [B, P, 2 H 64] GEMM output, the q slice of a fused q/k/v GEMM output).  `causal`: None for no
+    mask, or the position of query 0: query i then sees keys 0 .. causal + i.  Returns
+    [B, Tq, H, 64] contiguous on the current stream."""
+    return _prefill_attention("prefill_attention_f32", q, k, v, scale, causal, Tk, False)
+
+
+def prefill_attention_h16(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, causal: Optional[int] = None,
+                          Tk: Optional[int] = None) -> torch.Tensor:
+    """wx_prefill_attention_h16: prefill_attention_f32 on fp16 or bf16 device views of one dtype
+    (head dim contiguous, every other stride a multiple of 8 elements, 16-byte aligned).  Returns
+    [B, Tq, H, 64] contiguous in that dtype: prefill_attention_f32 of the widened inputs, rounded
+    once."""
+    return _prefill_attention("prefill_attention_h16", q, k, v, scale, causal, Tk, True)
 
 
 class PackedSegments:

@@ -37,7 +37,10 @@ Greedy decoding (beam_size 1, temperature 0), beam search (asr.py:301-304: beam_
 length_penalty 1 are the reference's defaults) and language detection are built on it.  In beam
 search the G beams of a chunk are rows b G + g of the state; their cross-attention reads the chunk's
 one K_x / V_x (wx_decode_attention_f32_grouped), and the 2G best continuations of every chunk come
-from wx_beam_topk.  Temperature fallback, timestamps and the tokenizer are not built.
+from wx_beam_topk.  `prefill` runs n positions in one pass instead (the prompt of generate /
+beam_search / logits with prefill=True): the same layers on [B n, D] rows, with
+wx_prefill_attention_f32 for the n queries against the cache under a causal mask and against
+K_x / V_x.  Temperature fallback, timestamps and the tokenizer are not built.
 
 With `dtype` float16 or bfloat16 the decoder runs the reference's compute type too (asr.py:262).
 Rounded to dtype: the GEMMs (weights and biases once, at construction; q/k/v, out, fc1, fc2 and the
@@ -239,36 +242,47 @@ def _mlp(L: dict):
     return lambda y: F.linear(F.gelu(F.linear(y, *L["fc1"])), *L["fc2"])
 
 
-def _chain(h: torch.Tensor, stages: list, final, add_norm=None) -> torch.Tensor:
+def _chain(h: torch.Tensor, stages: list, final, add_norm=None, select=None) -> torch.Tensor:
     """The pre-LN residual stream: h = h + fn(LN(h)) for every stage (ln, fn), then LN_final(h).
     `ln` and `final` are (weight, bias) pairs.  With `add_norm` (_lib.add_layernorm on the HIP
     route) every add is fused with the norm after it: the first norm has no residual to add and
-    is a plain layer_norm, the last add has no sum to keep."""
+    is a plain layer_norm, the last add has no sum to keep.  `select` (a prefill that wants one
+    position's logits) picks the rows of the stream that the last stage and the final norm run on;
+    the last stage must then be row-wise (the MLP)."""
     D = (h.shape[-1],)
+    if select is None:
+        select = lambda t: t  # noqa: E731
     if add_norm is None:
-        for ln, fn in stages:
+        for i, (ln, fn) in enumerate(stages):
+            if i == len(stages) - 1:
+                h = select(h)
             h = h + fn(F.layer_norm(h, D, *ln, _LN_EPS))
-        return F.layer_norm(h, D, *final, _LN_EPS)
-    y = F.layer_norm(h, D, *(stages[0][0] if stages else final), _LN_EPS)
+        return F.layer_norm(h if stages else select(h), D, *final, _LN_EPS)
+    y = F.layer_norm(h if stages else select(h), D, *(stages[0][0] if stages else final), _LN_EPS)
     for (_, fn), (ln, _) in zip(stages, stages[1:]):
         y, h = add_norm(h, fn(y), *ln, _LN_EPS, want_sum=True)
-    return add_norm(h, stages[-1][1](y), *final, _LN_EPS) if stages else y
+    return add_norm(select(h), stages[-1][1](select(y)), *final, _LN_EPS) if stages else y
 
 
-def _chain_half(h: torch.Tensor, stages: list, final, dtype: torch.dtype, kernels: bool) -> torch.Tensor:
+def _chain_half(h: torch.Tensor, stages: list, final, dtype: torch.dtype, kernels: bool, select=None) -> torch.Tensor:
     """_chain with 16-bit stages: the stream h and every norm are fp32, a norm's output is rounded
     once to `dtype`, `fn` takes and returns `dtype`, and its result joins the stream as
     h + float(fn(y)); the final norm writes fp32.  On the HIP route the first norm and every fused
-    add-norm but the last are wx_add_layernorm_h16; the last add is wx_add_layernorm on float(fn(y))."""
+    add-norm but the last are wx_add_layernorm_h16; the last add is wx_add_layernorm on float(fn(y)).
+    `select`: _chain's."""
     D = (h.shape[-1],)
+    if select is None:
+        select = lambda t: t  # noqa: E731
     if not kernels or not stages:
-        for ln, fn in stages:
+        for i, (ln, fn) in enumerate(stages):
+            if i == len(stages) - 1:
+                h = select(h)
             h = h + fn(F.layer_norm(h, D, *ln, _LN_EPS).to(dtype)).float()
-        return F.layer_norm(h, D, *final, _LN_EPS)
+        return F.layer_norm(h if stages else select(h), D, *final, _LN_EPS)
     y = _lib.add_layernorm_h16(h, None, *stages[0][0], _LN_EPS, dtype)
     for (_, fn), (ln, _) in zip(stages, stages[1:]):
         y, h = _lib.add_layernorm_h16(h, fn(y), *ln, _LN_EPS, dtype, want_sum=True)
-    return _lib.add_layernorm(h, stages[-1][1](y).float(), *final, _LN_EPS)
+    return _lib.add_layernorm(select(h), stages[-1][1](select(y)).float(), *final, _LN_EPS)
 
 
 _DTYPES = (torch.float32, torch.float16, torch.bfloat16)
@@ -612,6 +626,90 @@ class WhisperDecoder:
                 for s in ((L["ln1"], self_attention(L, ck, cv)), (L["ln2"], cross_attention(L, kv)), (L["ln3"], _mlp(L)))]
 
     @torch.inference_mode()
+    def prefill(self, state: DecoderState, tokens, all_positions: bool = False) -> torch.Tensor:
+        """n positions for every chunk in one pass: tokens [B, n] (ids at positions state.pos ..
+        state.pos + n - 1, one row per chunk) -> the fp32 logits after the last of them as
+        [state.rows, V] (step's contract; for a state of G beams a chunk's row repeated over its
+        beams), or with `all_positions` the logits after every one of them as [B, n, V]; the state
+        moves on by n.  Per layer: one q/k/v GEMM on the B n rows, the k and v rows written into
+        the cache at their positions, wx_prefill_attention_f32 on the cache under the causal mask
+        (query i sees positions 0 .. state.pos + i), and again without a mask on the
+        cross-attention keys and values in place; the norms and the MLP on B n rows; the last MLP,
+        the final norm and the logits GEMM on the last position's rows only, unless
+        `all_positions`.  A float16 / bfloat16 decoder takes wx_prefill_attention_h16 and rounds
+        where step rounds.  The host route runs the same structure on torch's attention with a
+        boolean mask.  G = 1: any state.pos with state.pos + n <= max_target_positions (prefill in
+        pieces and prefill after steps are both legal).  G > 1: state.pos must be 0; a chunk's
+        beams are identical during the prompt, so the B chunks are computed through the caches'
+        [::G] rows, which are then copied to the chunk's other G - 1 beams.  The GEMMs run at
+        another row count than step's, so the logits agree with n steps to rounding, not bit for
+        bit.  Runs on the current stream."""
+        t = tokens if torch.is_tensor(tokens) else torch.as_tensor(tokens)
+        if t.dim() != 2 or int(t.shape[1]) < 1:
+            raise ValueError(f"WhisperDecoder.prefill: tokens must be [B, n] with n >= 1, got {tuple(t.shape)}")
+        return self._prefill(state, self._tokens(t, (state.B, int(t.shape[1])), "prefill"), bool(all_positions))
+
+    def _prefill(self, st: DecoderState, tok: torch.Tensor, all_positions: bool) -> torch.Tensor:
+        """prefill() on checked ids [B, n] (n >= 1) already on the device."""
+        B, G, P, D, H, pos, n = st.B, st.G, st.P, self.D, self.H, st.pos, int(tok.shape[1])
+        if pos + n > self.max_target_positions:
+            raise ValueError(f"WhisperDecoder.prefill: positions {pos} .. {pos + n - 1} run past max_target_positions "
+                             f"({self.max_target_positions})")
+        if G > 1 and pos != 0:
+            raise ValueError(f"WhisperDecoder.prefill: a state of {G} beams is prefilled at position 0 only (its beams "
+                             f"differ from position {pos} on)")
+        half = self.dtype != torch.float32
+        if st.kernels:
+            kernel = _lib.prefill_attention_h16 if half else _lib.prefill_attention_f32
+
+            def attend(q, k, v, causal=None, Tk=None):
+                return kernel(q, k, v, 0.125, causal=causal, Tk=Tk).view(B * n, D)
+        else:
+            def attend(q, k, v, causal=None, Tk=None):
+                mask = None
+                if causal is not None:  # query i at position causal + i sees keys 0 .. causal + i
+                    mask = torch.arange(Tk, device=q.device)[None, :] <= causal + torch.arange(n, device=q.device)[:, None]
+                o = F.scaled_dot_product_attention(q, k[:, :, :Tk], v[:, :, :Tk], attn_mask=mask, scale=0.125)
+                return o.transpose(1, 2).reshape(B * n, D)
+
+        def self_attention(L, ck, cv):
+            ck, cv = ck[::G], cv[::G]  # one row per chunk: views, in place
+
+            def fn(y):
+                qkv = F.linear(y, *L["qkv"]).view(B, n, 3, H, 64)  # one GEMM on [B n, D]
+                q, k, v = (qkv[:, :, j].transpose(1, 2) for j in range(3))  # [B, H, n, 64] views
+                ck[:, :, pos:pos + n].copy_(k)
+                cv[:, :, pos:pos + n].copy_(v)
+                return F.linear(attend(q, ck, cv, pos, pos + n), *L["out"])
+            return fn
+
+        def cross_attention(L, kv):
+            kx, vx = (kv[:, :, j * D:(j + 1) * D].view(B, P, H, 64).transpose(1, 2) for j in range(2))  # views, in place
+            return lambda y: F.linear(attend(F.linear(y, *L["q_x"]).view(B, n, H, 64).transpose(1, 2), kx, vx),
+                                      *L["out_x"])
+
+        stages = [s for L, kv, ck, cv in zip(self.layers, st.cross, st.self_k, st.self_v)
+                  for s in ((L["ln1"], self_attention(L, ck, cv)), (L["ln2"], cross_attention(L, kv)), (L["ln3"], _mlp(L)))]
+        select = None if all_positions else (lambda t: t.view(B, n, t.shape[-1])[:, n - 1])
+        with self._ctx():
+            e = F.embedding(tok, self.embed)
+            h = ((e.float() if half else e) + self.pos[pos:pos + n]).view(B * n, D)
+            if half:
+                y = _chain_half(h, stages, self.ln_f, self.dtype, st.kernels, select)
+                lg = F.linear(y.to(self.dtype), self.embed).float()
+            else:
+                y = _chain(h, stages, self.ln_f, _lib.add_layernorm if st.kernels else None, select)
+                lg = F.linear(y, self.embed)
+            if G > 1:  # the chunk's rows to its other beams
+                for cache in (*st.self_k, *st.self_v):
+                    rows = cache.view(B, G, H, self.max_target_positions, 64)[:, :, :, :n]
+                    rows[:, 1:].copy_(rows[:, :1].expand(B, G - 1, H, n, 64))
+            st.pos += n
+            if all_positions:
+                return lg.view(B, n, self.V)
+            return lg.repeat_interleave(G, 0) if G > 1 else lg
+
+    @torch.inference_mode()
     def reorder(self, state: DecoderState, parents) -> None:
         """Row r of every self-attention cache (positions < state.pos) becomes row parents[r]:
         `parents` are B G int64 ids in [0, B G), the rows the new beams continue.  A copy in place
@@ -633,14 +731,20 @@ class WhisperDecoder:
                 live.copy_(live.index_select(0, idx))
 
     @torch.inference_mode()
-    def logits(self, encoder_states: torch.Tensor, tokens, kernels: Optional[bool] = None) -> torch.Tensor:
+    def logits(self, encoder_states: torch.Tensor, tokens, kernels: Optional[bool] = None,
+               prefill: bool = False) -> torch.Tensor:
         """Teacher-forced logits: tokens [B, n] -> [B, n, V], entry [:, i] the logits of the token
-        after tokens[:, :i + 1] (n calls to step; there is no batched prefill)."""
+        after tokens[:, :i + 1]: n calls to step, or with `prefill` one call to
+        prefill(all_positions=True).  `prefill` is off by default: its GEMMs run on B n rows and
+        need not round as the stepwise ones do, and generate's tokens are pinned to the argmax of
+        this method's stepwise output exactly."""
         st = self.start(encoder_states, kernels)
         t = tokens if torch.is_tensor(tokens) else torch.as_tensor(tokens)
         if t.dim() != 2:
             raise ValueError(f"WhisperDecoder.logits: tokens must be [B, n], got {tuple(t.shape)}")
         tok = self._tokens(t, (st.B, int(t.shape[1])), "logits")
+        if prefill and int(t.shape[1]) >= 1:
+            return self._prefill(st, tok, True)
         out = torch.empty((st.B, int(t.shape[1]), self.V), dtype=torch.float32, device=self.device)
         for i in range(int(t.shape[1])):
             out[:, i] = self._step(st, tok[:, i])
@@ -658,7 +762,7 @@ class WhisperDecoder:
     @torch.inference_mode()
     def generate(self, encoder_states: torch.Tensor, prompt, eot: int, max_length: int = 448, suppress_tokens=(),
                  suppress_at_start=(), kernels: Optional[bool] = None, beam_size: int = 1, patience: float = 1.0,
-                 length_penalty: float = 1.0) -> list:
+                 length_penalty: float = 1.0, prefill: bool = False) -> list:
         """Greedy decoding (asr.py:53-62 at beam_size 1, temperature 0): `prompt` (a list of ids,
         the same for every row) is fed one id per step; then every step takes the argmax of the
         logits with `suppress_tokens` at -inf, and at the first generated position also
@@ -667,10 +771,13 @@ class WhisperDecoder:
         or prompt + generated ids number min(max_length, max_target_positions).  Returns the
         generated ids per row, without the prompt and without `eot`.  The completion check
         synchronises once per step.  `beam_size` > 1: the ids of beam_search's best hypothesis of
-        every row (`patience` and `length_penalty` are beam_search's; greedy decoding ignores them)."""
+        every row (`patience` and `length_penalty` are beam_search's; greedy decoding ignores them).
+        `prefill`: the prompt goes through one call to prefill instead of one step per id.  Off by
+        default: prefill's GEMMs run at another row count and need not round as the stepwise ones
+        do, so the default keeps the tokens it gives today, bit for bit."""
         if int(beam_size) != 1:
             hyps = self.beam_search(encoder_states, prompt, eot, beam_size, patience, length_penalty, max_length,
-                                    suppress_tokens, suppress_at_start, kernels)
+                                    suppress_tokens, suppress_at_start, kernels, prefill)
             return [h[0].ids if h else [] for h in hyps]
         prompt = [int(t) for t in prompt]
         eot = int(eot)
@@ -685,8 +792,11 @@ class WhisperDecoder:
         limit = min(int(max_length), self.max_target_positions)
         if B == 0 or len(prompt) >= limit:
             return [[] for _ in range(B)]
-        for i in range(len(prompt)):
-            lg = self._step(st, ptok[:, i])
+        if prefill:
+            lg = self._prefill(st, ptok, False)
+        else:
+            for i in range(len(prompt)):
+                lg = self._step(st, ptok[:, i])
         done = torch.zeros(B, dtype=torch.bool, device=self.device)
         steps = []
         while True:
@@ -724,7 +834,7 @@ class WhisperDecoder:
     @torch.inference_mode()
     def beam_search(self, encoder_states: torch.Tensor, prompt, eot: int, beam_size: int = 5, patience: float = 1.0,
                     length_penalty: float = 1.0, max_length: int = 448, suppress_tokens=(), suppress_at_start=(),
-                    kernels: Optional[bool] = None) -> list:
+                    kernels: Optional[bool] = None, prefill: bool = False) -> list:
         """Beam search (asr.py:301-304: the reference's default is beam_size 5, patience 1,
         length_penalty 1).  The structure is that of OpenAI's BeamSearchDecoder and
         MaximumLikelihoodRanker; this docstring is the specification.
@@ -745,7 +855,9 @@ class WhisperDecoder:
         score = sum / n ** length_penalty with n the scored positions (the ids, plus one for an
         `eot`; at least 1), ranked by score, earlier-found first on ties.  The self-attention
         caches follow the beams by `reorder`; the 2G scores and indices of every chunk are the one
-        host synchronisation of a step."""
+        host synchronisation of a step.  `prefill`: the prompt goes through one call to prefill on
+        the B chunks (a chunk's beams are identical during the prompt) instead of one step per id
+        on B G rows; off by default, as in generate."""
         prompt = [int(t) for t in prompt]
         eot, G = int(eot), int(beam_size)
         if not prompt:
@@ -766,8 +878,11 @@ class WhisperDecoder:
         if B == 0 or len(prompt) >= limit:
             return [[] for _ in range(B)]
         ptok = self._tokens(torch.tensor(prompt).unsqueeze(0).expand(R, -1), (R, len(prompt)), "beam_search")
-        for i in range(len(prompt)):
-            lg = self._step(st, ptok[:, i])
+        if prefill:
+            lg = self._prefill(st, ptok[::G], False)
+        else:
+            for i in range(len(prompt)):
+                lg = self._step(st, ptok[:, i])
         ninf = float("-inf")
         sums = [[0.0] + [ninf] * (G - 1) for _ in range(B)]
         ids = [[[] for _ in range(G)] for _ in range(B)]
