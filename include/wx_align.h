@@ -264,6 +264,15 @@ int wx_conv0_channel_norm(const float* x, int64_t S, int32_t K, int32_t stride, 
                           int32_t C, const float* gamma, const float* beta, float eps, int32_t gelu, float* y,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* wx_conv0_channel_norm with a 16-bit store (the half route of the emission producer): the same
+ * passes on the fp32 waveform, expression for expression; y is [Lout, C] of `dtype` (WX_DTYPE_F16 /
+ * WX_DTYPE_BF16, defined below), rounded to nearest even once on the store: bit for bit the rounding
+ * of wx_conv0_channel_norm's y.  The workspace is wx_conv0_channel_norm_workspace_bytes(Lout, C).  An
+ * unknown dtype is WX_E_INVALID; everything else is validated as wx_conv0_channel_norm does. */
+int wx_conv0_channel_norm_h16(const float* x, int64_t S, int32_t K, int32_t stride, const float* w, const float* bias,
+                              int32_t C, const float* gamma, const float* beta, float eps, int32_t gelu, int32_t dtype,
+                              void* y, void* workspace, size_t workspace_bytes, void* stream);
+
 /* wav2vec2 self-attention (alignment.py:226-233, the emission forward's encoder layers):
  * o[b, t, h, :] = softmax(scale * q[b, h, t, :] . k[b, h, :, :]^T) v[b, h, :, :], fp32, no mask,
  * head dim D = 64 only.  q/k/v are [B, H, T, 64] with element strides {batch, head, time}
@@ -306,6 +315,26 @@ int wx_attention_f32_packed(const float* q, const float* k, const float* v, floa
                             const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, float scale,
                             int32_t split, void* stream);
 
+/* wx_attention_h16 over nseg segments packed back to back in one launch (the half route of the
+ * emission producer's packed encoder), with wx_attention_f32_packed's calling convention: seg_rows
+ * (device int32, nseg + 1): segment s owns rows [seg_rows[s], seg_rows[s + 1]); seg_units (device
+ * int32, nseg + 1): prefix of H * ceil(T_s / 64) (this kernel's unit is 64 queries), n_units its last
+ * entry.  q/k/v are [1, H, rows, 64] views of fp16 / bf16 elements with element strides {head, row}
+ * (*_strides[0..1], multiples of 8; pointers 16-byte aligned): the three slices of the fused
+ * [rows, 3 * 64 H] q/k/v GEMM output are read in place.  o is [rows, H, 64] contiguous in the same
+ * type.  Rows [seg_rows[s], seg_rows[s + 1]) of o are bit for bit what wx_attention_h16 returns for
+ * that segment alone (B = 1, T = T_s, the same views offset to the segment): the same per-wave key
+ * tiles and merge order.  They depend neither on nseg, nor on the other segments' contents, nor on
+ * the segment's position in the pack.  A segment of T_s = 0 is legal and owns no unit.  No address
+ * outside a segment's own rows is loaded for that segment; K / V rows at and past T_s enter as zeros.
+ * Validation, before anything is enqueued: nseg < 0, H < 1, D != 64, an unknown dtype, n_units < 0
+ * or a null q / k / v / o / stride pointer is WX_E_INVALID; then nseg == 0 or n_units == 0 is WX_OK;
+ * then a null table, a misaligned pointer or a stride that is no multiple of 8 is WX_E_INVALID. */
+int wx_attention_h16_packed(const void* q, const void* k, const void* v, void* o, int32_t nseg,
+                            const int32_t* seg_rows, const int32_t* seg_units, int32_t n_units, int32_t H, int32_t D,
+                            const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, float scale,
+                            int32_t dtype, void* stream);
+
 /* wav2vec2 positional convolution over packed segments (alignment.py:226-233: the encoder's
  * Wav2Vec2PositionalConvEmbedding, run per segment): for each segment s (rows [seg_rows[s],
  * seg_rows[s + 1]) of h [rows, D], 16-byte aligned) out[t] = GELU_erf(bias + conv(h)[t]) (+ h[t]
@@ -340,6 +369,16 @@ int wx_add_layernorm(const float* a, const float* b, int64_t rows, int32_t D, in
 int wx_add_layernorm_h16(const float* a, const void* b, int64_t rows, int32_t D, int64_t a_stride, int64_t b_stride,
                          const float* gamma, const float* beta, float eps, int32_t dtype, void* y, float* sum_out,
                          void* stream);
+
+/* wx_add_layernorm_h16 with both forms of the norm's output, for the post-norm wav2vec2 layers of
+ * the emission producer's half route (norm(residual + x) is the next residual in fp32 and the next
+ * GEMM operand in 16 bit): s = a + float(b), or s = a when b is NULL; y32 (fp32 [rows][D], may be
+ * NULL) is bit for bit wx_add_layernorm(a, float(b))'s y, y16 ([rows][D] of `dtype`) its rounding to
+ * nearest even, which is wx_add_layernorm_h16's y; sum_out (fp32, may be NULL) receives s.  One pass
+ * over the row.  Widths, alignment rules and the validation order are wx_add_layernorm_h16's. */
+int wx_add_layernorm_h16_dual(const float* a, const void* b, int64_t rows, int32_t D, int64_t a_stride,
+                              int64_t b_stride, const float* gamma, const float* beta, float eps, int32_t dtype,
+                              float* y32, void* y16, float* sum_out, void* stream);
 
 /* VAD producer (vad.py:198-240 -> pyannote SincNet): the epilogue of one SincNet stage on the
  * time-major conv output x [B windows][L][C] (window stride x_window_stride elements, row

@@ -117,6 +117,12 @@ SIGNATURES = {
     "wx_beam_topk": (ctypes.c_int, [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "wx_attention_h16": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _i32, _vp]),
     "wx_add_layernorm_h16": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _f32, _i32, _vp, _vp, _vp]),
+    "wx_attention_h16_packed": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp,
+                                               _f32, _i32, _vp]),
+    "wx_add_layernorm_h16_dual": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i64, _i64, _vp, _vp, _f32, _i32, _vp, _vp, _vp,
+                                                 _vp]),
+    "wx_conv0_channel_norm_h16": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _f32, _i32, _i32, _vp,
+                                                 _vp, _sz, _vp]),
     "wx_decode_attention_h16": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32, _i32, _vp,
                                                _sz, _vp]),
     "wx_decode_attention_h16_grouped": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32,
@@ -1170,7 +1176,8 @@ def prefill_attention_h16(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, sca
 class PackedSegments:
     """Row layout of segments packed back to back (the packed encoder's batch): host lengths
     and, per device, the int32 tables wx_attention_f32_packed reads — seg_rows (row offsets) and
-    seg_units (prefix of H x 32-query tiles), uploaded once per (device, H)."""
+    seg_units (prefix of H x 32-query tiles; 64-query units for wx_attention_h16_packed), uploaded
+    once per (device, H, rows per unit)."""
 
     def __init__(self, lengths):
         self.lengths = [int(t) for t in lengths]
@@ -1236,3 +1243,91 @@ def posconv_packed(h: torch.Tensor, w_packed: torch.Tensor, bias, G: int, K: int
                                      int(K), len(segs.lengths), _ptr(rows_t), _ptr(tiles_t), n_tiles,
                                      int(bool(residual)), _ptr(out), _stream(h.device)))
     return out
+
+
+def attention_h16_packed(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float,
+                         segs: PackedSegments) -> torch.Tensor:
+    """wx_attention_h16_packed: per-segment softmax(scale * q k^T) v over segments packed along the
+    row axis of [1, H, rows, 64] fp16 or bf16 device views of one dtype (head dim contiguous, head /
+    row strides multiples of 8, 16-byte aligned: the slices of the fused q/k/v GEMM output as they
+    are).  Returns [1, rows, H, 64] in that dtype; a segment's rows are bit for bit attention_h16's
+    on that segment alone."""
+    lib = load()
+    code = HALF_DTYPES.get(q.dtype)
+    if code is None or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise WXError(f"attention_h16_packed: q/k/v must share one of float16 / bfloat16, got {q.dtype}, {k.dtype}, "
+                      f"{v.dtype}")
+    B, H, R, D = (int(x) for x in q.shape)
+    if B != 1 or R != segs.rows or tuple(k.shape) != (1, H, R, D) or tuple(v.shape) != (1, H, R, D):
+        raise WXError(f"attention_h16_packed: q/k/v {tuple(q.shape)} / {tuple(k.shape)} / {tuple(v.shape)} "
+                      f"do not cover the {segs.rows} packed rows")
+    if any(t.stride(3) != 1 for t in (q, k, v)) and D > 1:
+        raise WXError("attention_h16_packed: the head dim must be contiguous")
+    o = torch.empty((1, R, H, D), dtype=q.dtype, device=q.device)
+    if R == 0 and H >= 1 and D == 64:  # no unit: nothing to launch (and an empty tensor has no storage to point at)
+        return o
+    rows_t, units_t, n_units, _ = segs.tables(q.device, H, 64)
+    st = [(ctypes.c_int64 * 2)(int(t.stride(1)), int(t.stride(2))) for t in (q, k, v)]
+    with torch.cuda.device(q.device):
+        _check(lib.wx_attention_h16_packed(_ptr(q), _ptr(k), _ptr(v), _ptr(o), len(segs.lengths), _ptr(rows_t),
+                                           _ptr(units_t), n_units, H, D, st[0], st[1], st[2], float(scale), code,
+                                           _stream(q.device)))
+    return o
+
+
+def add_layernorm_h16_dual(a: torch.Tensor, b: Optional[torch.Tensor], gamma: torch.Tensor, beta: torch.Tensor,
+                           eps: float, dtype: torch.dtype, want_y32: bool = True, want_sum: bool = False):
+    """wx_add_layernorm_h16_dual: LayerNorm(a + float(b)) (b None: LayerNorm(a)) over the last dim in
+    one pass, a fp32 and b of `dtype`.  Returns (y32, y16): the norm in fp32 (None without want_y32)
+    and its rounding to `dtype`; with want_sum (y32, y16, a + float(b))."""
+    lib = load()
+    code = HALF_DTYPES.get(dtype)
+    if code is None or a.dtype != torch.float32 or (b is not None and b.dtype != dtype):
+        raise WXError(f"add_layernorm_h16_dual: a must be float32 and b float16 / bfloat16 as `dtype` says, got "
+                      f"{a.dtype}, {None if b is None else b.dtype}, dtype {dtype}")
+    D = int(a.shape[-1])
+    if b is not None and tuple(a.shape) != tuple(b.shape):
+        raise WXError(f"add_layernorm_h16_dual: shapes differ ({tuple(a.shape)}, {tuple(b.shape)})")
+
+    def rows_of(t, mult):  # 16-byte aligned rows, or a contiguous copy (as add_layernorm)
+        t = t.reshape(-1, D)
+        return t if t.data_ptr() % 16 == 0 and (t.shape[0] <= 1 or t.stride(0) % mult == 0) and t.stride(1) == 1 \
+            else t.contiguous()
+    a2, b2 = rows_of(a, 4), None if b is None else rows_of(b, 8)
+    rows = int(a2.shape[0])
+    y32 = torch.empty(a.shape, dtype=torch.float32, device=a.device) if want_y32 else None
+    y16 = torch.empty(a.shape, dtype=dtype, device=a.device)
+    s = torch.empty(a.shape, dtype=torch.float32, device=a.device) if want_sum else None
+    with torch.cuda.device(a.device):
+        _check(lib.wx_add_layernorm_h16_dual(_ptr(a2), _ptr(b2), rows, D, int(a2.stride(0)) if rows else D,
+                                             int(b2.stride(0)) if rows and b2 is not None else D, _ptr(gamma),
+                                             _ptr(beta), float(eps), code, _ptr(y32), _ptr(y16), _ptr(s),
+                                             _stream(a.device)))
+    return (y32, y16, s) if want_sum else (y32, y16)
+
+
+def conv0_channel_norm_h16(x: torch.Tensor, w: torch.Tensor, bias, stride: int, gamma, beta, eps: float, gelu: bool,
+                           dtype: torch.dtype, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """wx_conv0_channel_norm_h16: conv0_channel_norm on the fp32 samples x [S] with the [Lout, C]
+    output stored in `dtype` (float16 / bfloat16): bit for bit the rounding of conv0_channel_norm's."""
+    lib = load()
+    code = HALF_DTYPES.get(dtype)
+    if code is None or x.dtype != torch.float32 or (out is not None and (out.dtype != dtype or not out.is_contiguous())):
+        raise WXError(f"conv0_channel_norm_h16: x must be float32 and the output contiguous float16 / bfloat16, got "
+                      f"{x.dtype}, dtype {dtype}, out {None if out is None else out.dtype}")
+    S = int(x.shape[-1])
+    C, K = int(w.shape[0]), int(w.shape[-1])
+    w2 = w.reshape(C, K).contiguous()
+    L = (S - K) // stride + 1 if S >= K else 0
+    if out is not None and tuple(out.shape) != (L, C):
+        raise WXError(f"conv0_channel_norm_h16: out is {tuple(out.shape)}, the output is {(L, C)}")
+    y = out if out is not None else torch.empty((L, C), dtype=dtype, device=x.device)
+    if L == 0:
+        return y
+    stream = torch.cuda.current_stream(x.device)
+    ws = _scratch.get("conv0", x.device, lib.wx_conv0_channel_norm_workspace_bytes(L, C), stream)
+    with torch.cuda.device(x.device):
+        _check(lib.wx_conv0_channel_norm_h16(_ptr(x), S, K, int(stride), _ptr(w2), _ptr(bias) if bias is not None else None,
+                                             C, _ptr(gamma), _ptr(beta), float(eps), int(bool(gelu)), code, _ptr(y),
+                                             _ptr(ws), ws.numel(), ctypes.c_void_p(stream.cuda_stream)))
+    return y

@@ -30,6 +30,7 @@ import contextlib
 import math
 import os
 import time
+import warnings
 from dataclasses import dataclass
 from typing import Callable, Iterable, List, Optional, Union
 
@@ -86,9 +87,38 @@ DEFAULT_ALIGN_MODELS_HF = {
 
 
 # ------------------------------------------------------------------------------- loading
-def load_align_model(language_code, device, model_name=None, model_dir=None):
+_ALIGN_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def _half_dtype(metadata: dict):
+    """The half dtype an align model's metadata asks for (its "dtype" key), None for fp32 / absent."""
+    dtype = metadata.get("dtype")
+    if dtype is None or dtype == torch.float32:
+        return None
+    if dtype not in _ALIGN_DTYPES:
+        raise ValueError(f"align model dtype must be torch.float32, torch.float16 or torch.bfloat16, not {dtype!r}")
+    return dtype
+
+
+def _check_half_model(model, model_type, dtype):
+    """ValueError unless the half route can run this model (never a silent fp32 run); builds and
+    caches its rounded operands (a weight that overflows the type is refused here, by name)."""
+    if model_type != "huggingface":
+        raise ValueError(f"dtype {dtype} needs a Hugging Face Wav2Vec2ForCTC align model: the half route runs the "
+                         f"packed encoder, which does not run {model_type} models")
+    emission.half_operands(model, dtype)
+
+
+def load_align_model(language_code, device, model_name=None, model_dir=None, dtype=torch.float32):
     """alignment.py:64-97.  torchaudio bundles when torchaudio is installed; otherwise a
-    Hugging Face Wav2Vec2ForCTC from a hub name or (offline) a local directory."""
+    Hugging Face Wav2Vec2ForCTC from a hub name or (offline) a local directory.
+
+    `dtype` torch.float16 / torch.bfloat16 (an extension; the reference has no such keyword): the
+    model stays fp32, and align() runs its forward on the half route of the packed encoder
+    (emission.packed_logits); recorded as align_metadata["dtype"].  ValueError for any other dtype
+    and for a model that route cannot run."""
+    if dtype not in _ALIGN_DTYPES:
+        raise ValueError(f"load_align_model: dtype must be torch.float32, torch.float16 or torch.bfloat16, not {dtype!r}")
     if model_name is None:
         if language_code in DEFAULT_ALIGN_MODELS_TORCH:
             model_name = DEFAULT_ALIGN_MODELS_TORCH[language_code]
@@ -123,6 +153,9 @@ def load_align_model(language_code, device, model_name=None, model_dir=None):
         align_dictionary = {char.lower(): code for char, code in processor.tokenizer.get_vocab().items()}
 
     align_metadata = {"language": language_code, "dictionary": align_dictionary, "type": pipeline_type}
+    if dtype != torch.float32:
+        _check_half_model(align_model, pipeline_type, dtype)
+        align_metadata["dtype"] = dtype
     return align_model, align_metadata
 
 
@@ -306,20 +339,41 @@ def _vocab_size(model, model_type):
 _EMISSION_STREAMS = {}
 
 
+def _emissions_half_host(model, waveforms, dtype):
+    """The half route's emissions of a model on the CPU (emission.packed_logits in torch ops):
+    one [T, V] log-probability matrix per segment."""
+    Ts = [emission.n_frames(int(w.shape[-1]), model) for w in waveforms]
+    if not waveforms:
+        return []
+    lg = emission.packed_logits(model, waveforms, _lib.PackedSegments(Ts), None, dtype=dtype)
+    with torch.inference_mode():
+        return list(torch.log_softmax(lg, -1).split(Ts))
+
+
 def _emissions(model, model_type, waveforms, device, n_streams: int = int(os.environ.get("WX_EMISSION_STREAMS", "8")),
-               allow_packed: bool = True):
+               allow_packed: bool = True, dtype=None):
     """Emissions of every segment, one unpadded forward each (padding would change wav2vec2's
     logits, alignment.py:217-233), issued round-robin on `n_streams` (8; A/B on config 3: 2 / 4 / 8 streams 803 / 790 / 755 ms) HIP streams: one 30 s
     forward's GEMMs (1,499 rows) fill a fraction of the GPU, so consecutive segments overlap.
     On a HIP device each forward's log_softmax writes straight into its rows of one packed
     [sum_T, V] matrix (returned as _EmissionsCSR), which the DP reads in place; the model's
     convolutions take the length-agnostic GEMM route (emission.prepare_model) unless
-    WX_MIOPEN_CONV=1.  Joined back onto the current stream."""
+    WX_MIOPEN_CONV=1.  Joined back onto the current stream.
+    `dtype` float16 / bfloat16: the half route of the packed encoder (the only half route there
+    is: ValueError where it cannot run); None or float32: everything as it was."""
     dev = torch.device(device) if not isinstance(device, torch.device) else device
+    if dtype == torch.float32:
+        dtype = None
+    if dtype is not None:
+        _check_half_model(model, model_type, dtype)
+        if dev.type != "cuda":
+            return _emissions_half_host(model, waveforms, dtype)
     if dev.type != "cuda":
         return [_emission(model, model_type, w, device) for w in waveforms]
     packed = (allow_packed and not os.environ.get("WX_MIOPEN_CONV") and model_type == "huggingface"
               and emission.packed_supported(model))
+    if dtype is not None and not packed:
+        raise ValueError("the half route runs the packed encoder only (allow_packed=False or WX_MIOPEN_CONV given)")
     if not os.environ.get("WX_MIOPEN_CONV") and not packed:
         emission.prepare_model(model)
         # cached weight_norm weights are built here, on the current stream, before the
@@ -344,7 +398,7 @@ def _emissions(model, model_type, waveforms, device, n_streams: int = int(os.env
     if packed:
         try:
             csr.groups = _pack_ranges(Ts)
-            csr.events = _packed_emissions(model, waveforms, csr, streams)
+            csr.events = _packed_emissions(model, waveforms, csr, streams, dtype)
             csr.streams = streams
             return csr
         except ValueError:  # a model whose frame geometry is not n_frames': per-segment path
@@ -414,7 +468,7 @@ def _pack_ranges(Ts, cap: Optional[int] = None):
     return packs
 
 
-def _packed_emissions(model, waveforms, csr, streams):
+def _packed_emissions(model, waveforms, csr, streams, dtype=None):
     """The packed-encoder route of _emissions (emission.packed_logits): segments in the packs
     csr.groups (consecutive ranges, _pack_ranges), all on streams[0] (the others only serve
     packed_logits' per-segment feature-encoder fallback), log_softmax of the whole pack into
@@ -425,7 +479,11 @@ def _packed_emissions(model, waveforms, csr, streams):
     ps = streams[0]
     for a, b in csr.groups:
         with torch.cuda.stream(ps):
-            lg = emission.packed_logits(model, waveforms[a:b], _lib.PackedSegments(csr.Ts[a:b]), streams)
+            segs = _lib.PackedSegments(csr.Ts[a:b])
+            if dtype is None:
+                lg = emission.packed_logits(model, waveforms[a:b], segs, streams)
+            else:
+                lg = emission.packed_logits(model, waveforms[a:b], segs, streams, dtype=dtype)
             with torch.inference_mode():
                 emission.log_softmax_into(lg, csr.em[csr.off[a]: csr.off[b]])
             ev = torch.cuda.Event()
@@ -477,6 +535,10 @@ def align(
     model_dictionary = align_model_metadata["dictionary"]
     model_lang = align_model_metadata["language"]
     model_type = align_model_metadata["type"]
+    # load_align_model(dtype=...)'s key: the forward on the half route of the packed encoder
+    half = _half_dtype(align_model_metadata)
+    if half is not None:
+        _check_half_model(model, model_type, half)
 
     # 2a. the emission forward of every segment that starts inside the audio, queued on the
     # device first, so that the host prepares the transcripts (step 1) while the GPU runs them.
@@ -510,8 +572,11 @@ def align(
             model_ctx.enter_context(emission.prepared(model))
         with _Phase("emission"):
             try:
-                ems = _emissions(model, model_type, wavs, device)
+                ems = _emissions(model, model_type, wavs, device, dtype=half)
             except _PackedUnsupported:  # per-segment route, model prepared for this call
+                if half is not None:  # (the per-segment route has no half form)
+                    warnings.warn(f"align: the packed encoder refused this call's frame geometry; its forwards run "
+                                  f"in float32 on the per-segment route, not in {half}", RuntimeWarning, stacklevel=2)
                 model_ctx.enter_context(emission.prepared(model))
                 ems = _emissions(model, model_type, wavs, device, allow_packed=False)
 

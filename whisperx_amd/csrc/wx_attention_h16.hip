@@ -1,7 +1,9 @@
 // wx_attention_h16.hip — Whisper's encoder self-attention on 16-bit inputs (whisperx/asr.py:262: the
 // reference loads its model with compute_type="float16"): softmax(scale q k^T) v for fp16 or bf16
 // q / k / v, no mask, head dim 64, on v_mfma_f32_32x32x16_{f16,bf16}.  C ABI and semantics:
-// include/wx_align.h (wx_attention_h16).
+// include/wx_align.h (wx_attention_h16).  wx_attention_h16_packed runs the same body over segments
+// packed back to back (the half route of the wav2vec2 emission forward, alignment.py:217-233: one
+// unpadded forward per segment), each segment bit for bit as if launched alone.
 //
 // The structure is attn_f32_kernel's (wx_emission.hip): one workgroup per (batch, head, query tile),
 // whose kSplit waves each take every kSplit-th 32-key tile and merge their (max, sum, O) states
@@ -87,35 +89,21 @@ __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_wave_barrier();
 }
 
-// amdgpu_waves_per_eu(2): 223 VGPRs, no spill.  With one query tile per wave (141 VGPRs) two, three
-// and four waves per SIMD measured the same to 1%, as did whole key tiles loaded without the row
-// compares: the kernel was bound by the K / V traffic from L2 (8 KB per wave and key tile for 4 + 4
-// MFMAs), which the second query tile halves (B 16, T 1500, fp16: H 8 0.198 -> 0.173 ms, H 20
-// 0.440 -> 0.380 ms).
+// One (head, 64-query tile) unit of one batch entry or packed segment: Q / K / V point at row 0 of
+// that (entry, head) (row strides sqt / skt / svt), O at its output row 0 (row stride orow elements),
+// T is its length.  Both entry points below resolve these and run the same body, so a segment of a
+// pack is computed exactly as the same rows alone (same per-wave key tiles, same merge order).
 template <bool BF>
-__global__ __launch_bounds__(64 * kSplit) __attribute__((amdgpu_waves_per_eu(2))) void attn_h16_kernel(AttnH16Args a) {
-    __shared__ __attribute__((aligned(16))) char lds[kLdsBytes];
-    const int T = a.T;
-    // 1-D grid, block L runs on XCD L % 8: hand each XCD a contiguous run of (head, query tile)
-    // units, so the blocks sharing one head's K / V meet in one XCD's L2 (as attn_f32_kernel)
-    const unsigned w = [] {
-        const unsigned L = blockIdx.x, n = gridDim.x, x = L % 8, i = L / 8, q = n / 8, r = n % 8;
-        return x * q + min(x, r) + i;
-    }();
-    const int nq = (T + kQueries - 1) / kQueries;
-    const int tile = (int)(w % (unsigned)nq);
-    const int bh = (int)(w / (unsigned)nq);
-    const int b = bh / a.H, h = bh % a.H;
-    const short* Q = a.q + b * a.sqb + h * a.sqh;
-    const short* K = a.k + b * a.skb + h * a.skh;
-    const short* V = a.v + b * a.svb + h * a.svh;
+__device__ __forceinline__ void attn_h16_unit(const short* Q, const short* K, const short* V, short* O, const int T,
+                                              const int tile, const int64_t sqt, const int64_t skt, const int64_t svt,
+                                              const int64_t orow, const float scale_log2, char* lds) {
     const int q0 = tile * kQueries;
     const int l = threadIdx.x & 63, r = l & 31, hf = l >> 5;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (uniform, which hipcc cannot prove)
     s16x8 qf[kNQ][4];  // query q0 + 32 u + r (past the end: the last row again, never stored)
 #pragma unroll
     for (int u = 0; u < kNQ; ++u) {
-        const s16x8* qp = reinterpret_cast<const s16x8*>(Q + (int64_t)min(q0 + 32 * u + r, T - 1) * a.sqt + 32 * hf);
+        const s16x8* qp = reinterpret_cast<const s16x8*>(Q + (int64_t)min(q0 + 32 * u + r, T - 1) * sqt + 32 * hf);
 #pragma unroll
         for (int t = 0; t < 4; ++t) qf[u][t] = qp[t];
     }
@@ -128,7 +116,6 @@ __global__ __launch_bounds__(64 * kSplit) __attribute__((amdgpu_waves_per_eu(2))
         m[u] = -INFINITY;
         lsum[u] = 0.f;
     }
-    const int64_t skt = a.skt, svt = a.svt;
     // V tile in LDS: row `key`, 16-byte chunk c (8 per row) at 128 key + 16 (c ^ 4 ((key >> 1) & 1))
     char* vt = lds + wv * kTileBytes;
     const int vrow = l >> 3, vch = l & 7;  // this lane's chunk of rows vrow + 8 i in the global loads
@@ -187,14 +174,14 @@ __global__ __launch_bounds__(64 * kSplit) __attribute__((amdgpu_waves_per_eu(2))
             if (k0 + 32 <= T) {  // a whole key tile: no key compare (uniform branch)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
-                    s[u][i] = s[u][i] * a.scale_log2;
+                    s[u][i] = s[u][i] * scale_log2;
                     mx = fmaxf(mx, s[u][i]);
                 }
             } else {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
                     const int key = k0 + (i & 3) + 8 * (i >> 2) + 4 * hf;
-                    const float x = key < T ? s[u][i] * a.scale_log2 : -INFINITY;
+                    const float x = key < T ? s[u][i] * scale_log2 : -INFINITY;
                     s[u][i] = x;
                     mx = fmaxf(mx, x);
                 }
@@ -289,7 +276,7 @@ __global__ __launch_bounds__(64 * kSplit) __attribute__((amdgpu_waves_per_eu(2))
         const int qi = q0 + 32 * u + r;
         if (qi >= T) continue;
         const float inv = 1.0f / lsum[u];
-        short* orow = a.o + (((int64_t)b * T + qi) * a.H + h) * 64;
+        short* orow_p = O + (int64_t)qi * orow;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {  // registers 4g..4g+3: head dims 8g + 4hf + 0..3
             const int d = 8 * g + 4 * hf;
@@ -299,10 +286,72 @@ __global__ __launch_bounds__(64 * kSplit) __attribute__((amdgpu_waves_per_eu(2))
                 x0[j] = round16<BF>(o0[u][4 * g + j] * inv);
                 x1[j] = round16<BF>(o1[u][4 * g + j] * inv);
             }
-            *reinterpret_cast<s16x4*>(orow + d) = x0;
-            *reinterpret_cast<s16x4*>(orow + 32 + d) = x1;
+            *reinterpret_cast<s16x4*>(orow_p + d) = x0;
+            *reinterpret_cast<s16x4*>(orow_p + 32 + d) = x1;
         }
     }
+}
+
+
+// 1-D grid, block L runs on XCD L % 8: hand each XCD a contiguous run of (head, query tile)
+// units, so the blocks sharing one head's K / V meet in one XCD's L2 (as attn_f32_kernel)
+__device__ __forceinline__ unsigned xcd_unit() {
+    const unsigned L = blockIdx.x, n = gridDim.x, x = L % 8, i = L / 8, q = n / 8, r = n % 8;
+    return x * q + min(x, r) + i;
+}
+
+// amdgpu_waves_per_eu(2): 223 VGPRs, no spill.  With one query tile per wave (141 VGPRs) two, three
+// and four waves per SIMD measured the same to 1%, as did whole key tiles loaded without the row
+// compares: the kernel was bound by the K / V traffic from L2 (8 KB per wave and key tile for 4 + 4
+// MFMAs), which the second query tile halves (B 16, T 1500, fp16: H 8 0.198 -> 0.173 ms, H 20
+// 0.440 -> 0.380 ms).
+template <bool BF>
+__global__ __launch_bounds__(64 * kSplit) __attribute__((amdgpu_waves_per_eu(2))) void attn_h16_kernel(AttnH16Args a) {
+    __shared__ __attribute__((aligned(16))) char lds[kLdsBytes];
+    const int T = a.T;
+    const unsigned w = xcd_unit();
+    const int nq = (T + kQueries - 1) / kQueries;
+    const int tile = (int)(w % (unsigned)nq);
+    const int bh = (int)(w / (unsigned)nq);
+    const int b = bh / a.H, h = bh % a.H;
+    attn_h16_unit<BF>(a.q + b * a.sqb + h * a.sqh, a.k + b * a.skb + h * a.skh, a.v + b * a.svb + h * a.svh,
+                      a.o + ((int64_t)b * T * a.H + h) * 64, T, tile, a.sqt, a.skt, a.svt, (int64_t)a.H * 64,
+                      a.scale_log2, lds);
+}
+
+// wx_attention_h16_packed: segment s owns rows [seg_rows[s], seg_rows[s + 1]) of q / k / v / o and
+// units [seg_units[s], seg_units[s + 1]) of the grid (H x its 64-query tiles, head-major, so that
+// one (segment, head)'s units are a contiguous run of one XCD)
+struct AttnH16PackedArgs {
+    const short *q, *k, *v;
+    short* o;  // [rows, H, 64]
+    int H, nseg;
+    int64_t sqh, sqt, skh, skt, svh, svt;  // element strides (head dim: 1)
+    float scale_log2;
+    const int32_t* seg_rows;
+    const int32_t* seg_units;
+};
+
+template <bool BF>
+__global__ __launch_bounds__(64 * kSplit) __attribute__((amdgpu_waves_per_eu(2))) void attn_h16_packed_kernel(
+    AttnH16PackedArgs a) {
+    __shared__ __attribute__((aligned(16))) char lds[kLdsBytes];
+    const unsigned w = xcd_unit();
+    // the segment owning unit w: the last s with seg_units[s] <= w (an empty segment owns no unit,
+    // so the last such s is never one of them: T >= 1 below)
+    int lo = 0, hi = a.nseg - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if ((unsigned)a.seg_units[mid] <= w) lo = mid;
+        else hi = mid - 1;
+    }
+    const int64_t row0 = a.seg_rows[lo];
+    const int T = a.seg_rows[lo + 1] - (int)row0;
+    const int nq = (T + kQueries - 1) / kQueries;
+    const int u = (int)w - a.seg_units[lo];
+    const int tile = u % nq, h = u / nq;
+    attn_h16_unit<BF>(a.q + row0 * a.sqt + h * a.sqh, a.k + row0 * a.skt + h * a.skh, a.v + row0 * a.svt + h * a.svh,
+                      a.o + (row0 * a.H + h) * 64, T, tile, a.sqt, a.skt, a.svt, (int64_t)a.H * 64, a.scale_log2, lds);
 }
 
 }  // namespace wxh
@@ -343,5 +392,44 @@ extern "C" int wx_attention_h16(const void* q, const void* k, const void* v, voi
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (dtype == WX_DTYPE_BF16) hipLaunchKernelGGL(attn_h16_kernel<true>, grid, dim3(64 * kSplit), 0, s, a);
     else hipLaunchKernelGGL(attn_h16_kernel<false>, grid, dim3(64 * kSplit), 0, s, a);
+    return wx::launch_status();
+}
+
+extern "C" int wx_attention_h16_packed(const void* q, const void* k, const void* v, void* o, int32_t nseg,
+                                       const int32_t* seg_rows, const int32_t* seg_units, int32_t n_units, int32_t H,
+                                       int32_t D, const int64_t* q_strides, const int64_t* k_strides,
+                                       const int64_t* v_strides, float scale, int32_t dtype, void* stream) {
+    using namespace wxh;
+    if (nseg < 0 || H <= 0 || D != 64 || (dtype != WX_DTYPE_F16 && dtype != WX_DTYPE_BF16) || n_units < 0 || !q || !k ||
+        !v || !o || !q_strides || !k_strides || !v_strides)
+        return WX_E_INVALID;
+    if (nseg == 0 || n_units == 0) return WX_OK;
+    if (!seg_rows || !seg_units) return WX_E_INVALID;
+    const int64_t* st[3] = {q_strides, k_strides, v_strides};
+    const void* pt[3] = {q, k, v};
+    for (int i = 0; i < 3; ++i) {  // 16-byte reads of 8 elements
+        if ((reinterpret_cast<uintptr_t>(pt[i]) & 15) || (st[i][0] & 7) || (st[i][1] & 7)) return WX_E_INVALID;
+    }
+    if (reinterpret_cast<uintptr_t>(o) & 15) return WX_E_INVALID;
+    AttnH16PackedArgs a;
+    a.q = static_cast<const short*>(q);
+    a.k = static_cast<const short*>(k);
+    a.v = static_cast<const short*>(v);
+    a.o = static_cast<short*>(o);
+    a.H = H;
+    a.nseg = nseg;
+    a.sqh = q_strides[0];
+    a.sqt = q_strides[1];
+    a.skh = k_strides[0];
+    a.skt = k_strides[1];
+    a.svh = v_strides[0];
+    a.svt = v_strides[1];
+    a.scale_log2 = scale * 1.4426950408889634f;
+    a.seg_rows = seg_rows;
+    a.seg_units = seg_units;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)n_units);
+    if (dtype == WX_DTYPE_BF16) hipLaunchKernelGGL(attn_h16_packed_kernel<true>, grid, dim3(64 * kSplit), 0, s, a);
+    else hipLaunchKernelGGL(attn_h16_packed_kernel<false>, grid, dim3(64 * kSplit), 0, s, a);
     return wx::launch_status();
 }

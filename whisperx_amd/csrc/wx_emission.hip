@@ -194,11 +194,29 @@ __global__ __launch_bounds__(256) void conv0_finish_kernel(const double* __restr
 
 __device__ __forceinline__ float gelu_erf0(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
 
-template <int K>
+// The apply passes' store (OT: 0 fp32, else the WX_DTYPE_* code of wx_conv0_channel_norm_h16): the
+// fp32 value, computed by the same expressions whatever OT is, rounded to nearest even on the way out.
+template <int OT>
+struct C0Out {
+    using type = float;
+    static __device__ __forceinline__ float put(float v) { return v; }
+};
+template <>
+struct C0Out<WX_DTYPE_F16> {
+    using type = unsigned short;
+    static __device__ __forceinline__ unsigned short put(float v) { return __builtin_bit_cast(unsigned short, (_Float16)v); }
+};
+template <>
+struct C0Out<WX_DTYPE_BF16> {
+    using type = unsigned short;
+    static __device__ __forceinline__ unsigned short put(float v) { return __builtin_bit_cast(unsigned short, (__bf16)v); }
+};
+
+template <int K, int OT = 0>
 __global__ __launch_bounds__(256) void conv0_apply_kernel(const float* __restrict__ x, int64_t L, int stride,
                                                           const float* __restrict__ wt, int C,
                                                           const float* __restrict__ ab, int gelu,
-                                                          float* __restrict__ y) {
+                                                          typename C0Out<OT>::type* __restrict__ y) {
     const int c = blockIdx.x * kCols + (threadIdx.x & (kCols - 1));
     const int wv = threadIdx.x / kCols;
     if (c >= C) return;
@@ -213,7 +231,7 @@ __global__ __launch_bounds__(256) void conv0_apply_kernel(const float* __restric
         if (t >= L) break;
         float v = conv0_at<K>(x, t, stride, w) * sa + sb;
         if (gelu) v = gelu_erf0(v);
-        y[t * C + c] = v;
+        y[t * C + c] = C0Out<OT>::put(v);
     }
 }
 
@@ -309,11 +327,11 @@ __global__ __launch_bounds__(256) void conv0_stats_rl_kernel(const float* __rest
     }
 }
 
-template <int K, int S>
+template <int K, int S, int OT = 0>
 __global__ __launch_bounds__(256) void conv0_apply_rl_kernel(const float* __restrict__ x, int64_t nsamp, int64_t L,
                                                              const float* __restrict__ wt, int C,
                                                              const float* __restrict__ ab, int gelu,
-                                                             float* __restrict__ y) {
+                                                             typename C0Out<OT>::type* __restrict__ y) {
     const int lc = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int c = blockIdx.x * 64 + lc;
     const int cc = min(c, C - 1);
@@ -323,14 +341,14 @@ __global__ __launch_bounds__(256) void conv0_apply_rl_kernel(const float* __rest
     const float sa = ab[cc], sb = ab[C + cc];
     const int64_t t0 = ((int64_t)blockIdx.y * 4 + wv) * kC0R;
     const int64_t nr = L - t0;
-    float* yr = y + t0 * C + c;  // (row r at yr + r C)
+    typename C0Out<OT>::type* yr = y + t0 * C + c;  // (row r at yr + r C)
     if (t0 * S + (kC0R - 1) * S + K <= nsamp) {
         const float* xs = x + t0 * S;
 #pragma unroll
         for (int r = 0; r < kC0R; ++r) {
             float v = conv0_row_s<K, S>(xs, r, w) * sa + sb;
             if (gelu) v = gelu_erf0(v);
-            if (r < nr && c < C) yr[(int64_t)r * C] = v;
+            if (r < nr && c < C) yr[(int64_t)r * C] = C0Out<OT>::put(v);
         }
     } else {
         float sv[((kC0R - 1) * S + K + 63) / 64];
@@ -339,7 +357,7 @@ __global__ __launch_bounds__(256) void conv0_apply_rl_kernel(const float* __rest
         for (int r = 0; r < kC0R; ++r) {
             float v = conv0_row<K, S>(sv, r, w) * sa + sb;
             if (gelu) v = gelu_erf0(v);
-            if (r < nr && c < C) yr[(int64_t)r * C] = v;
+            if (r < nr && c < C) yr[(int64_t)r * C] = C0Out<OT>::put(v);
         }
     }
 }
@@ -726,6 +744,71 @@ __global__ __launch_bounds__(256) void add_ln_h16_kernel(const float* __restrict
     }
 }
 
+// add_ln_h16_kernel with both forms of the norm's output (wx_add_layernorm_h16_dual): a post-norm
+// wav2vec2 layer needs norm(residual + x) in fp32 as the next residual and in 16 bit as the next GEMM
+// operand.  One pass over the row: y32 (optional) is add_ln_kernel's y on float(b) bit for bit, y16
+// its rounding to nearest even (add_ln_h16_kernel's y); the expressions are theirs.
+template <bool BF, int NV, int D4 = 64 * NV>
+__global__ __launch_bounds__(256) void add_ln_dual_kernel(const float* __restrict__ a, const unsigned short* __restrict__ b,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           float eps, int64_t rows, int64_t sa, int64_t sb, int64_t sy,
+                                                           float* __restrict__ y32, unsigned short* __restrict__ y16,
+                                                           float* __restrict__ sum_out) {
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int l = threadIdx.x & 63;
+    constexpr int D = 4 * D4;
+    constexpr bool kFull = D4 == 64 * NV;
+    static_assert(D4 <= 64 * NV && D4 > 64 * (NV - 1), "NV float4 per lane cover the row");
+    const float4* pa = reinterpret_cast<const float4*>(a + row * sa);
+    const ushort4* pb = b ? reinterpret_cast<const ushort4*>(b + row * sb) : nullptr;
+    float4 v[NV];
+    float acc = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        if (!kFull && 64 * i + l >= D4) {
+            v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            continue;
+        }
+        const float4 x = pa[64 * i + l];
+        float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (pb) {
+            const ushort4 u = pb[64 * i + l];
+            z = make_float4(ln_widen16<BF>(u.x), ln_widen16<BF>(u.y), ln_widen16<BF>(u.z), ln_widen16<BF>(u.w));
+        }
+        v[i] = make_float4(x.x + z.x, x.y + z.y, x.z + z.z, x.w + z.w);
+        acc += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    const float mean = acc / (float)D;
+    float q = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        if (!kFull && 64 * i + l >= D4) continue;
+        const float dx = v[i].x - mean, dy = v[i].y - mean, dz = v[i].z - mean, dw = v[i].w - mean;
+        q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
+    const float rstd = 1.0f / sqrtf(q / (float)D + eps);
+    float4* p32 = y32 ? reinterpret_cast<float4*>(y32 + row * sy) : nullptr;
+    ushort4* p16 = reinterpret_cast<ushort4*>(y16 + row * sy);
+    float4* ps = sum_out ? reinterpret_cast<float4*>(sum_out + row * sy) : nullptr;
+    const float4* pg = reinterpret_cast<const float4*>(gamma);
+    const float4* pt = reinterpret_cast<const float4*>(beta);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        if (!kFull && 64 * i + l >= D4) continue;
+        const float4 g = pg[64 * i + l], t = pt[64 * i + l];
+        const float4 y = make_float4((v[i].x - mean) * rstd * g.x + t.x, (v[i].y - mean) * rstd * g.y + t.y,
+                                     (v[i].z - mean) * rstd * g.z + t.z, (v[i].w - mean) * rstd * g.w + t.w);
+        if (p32) p32[64 * i + l] = y;
+        p16[64 * i + l] = make_ushort4(ln_round16<BF>(y.x), ln_round16<BF>(y.y), ln_round16<BF>(y.z), ln_round16<BF>(y.w));
+        if (ps) ps[64 * i + l] = v[i];
+    }
+}
+
 // ------------------------------------------------------------------------------------
 // wav2vec2 positional convolution over packed segments (alignment.py:226-233: the encoder's
 // Wav2Vec2PositionalConvEmbedding — Conv1d(D, D, K = 128, padding K / 2, groups G), the last
@@ -909,12 +992,16 @@ extern "C" size_t wx_conv0_channel_norm_workspace_bytes(int64_t L, int32_t C) {
     return (size_t)nblk * 2 * C * sizeof(double) + 2 * (size_t)C * sizeof(float);
 }
 
-extern "C" int wx_conv0_channel_norm(const float* x, int64_t S, int32_t K, int32_t stride, const float* w,
-                                     const float* bias, int32_t C, const float* gamma, const float* beta, float eps,
-                                     int32_t gelu, float* y, void* workspace, size_t workspace_bytes, void* stream) {
-    using namespace wxe;
-    if (S < 0 || C <= 0 || K < 1 || K > kC0MaxK || stride < 1 || !x || !w || !y) return WX_E_INVALID;
-    (void)bias;  // cancels in the per-channel normalisation (see above): never added
+namespace wxe {
+
+// wx_conv0_channel_norm (OT 0, y fp32) and wx_conv0_channel_norm_h16 (OT a WX_DTYPE_* code, y 16 bit):
+// the same statistics passes, the apply pass instantiated for the output type
+template <int OT>
+static int conv0_channel_norm(const float* x, int64_t S, int32_t K, int32_t stride, const float* w, int32_t C,
+                              const float* gamma, const float* beta, float eps, int32_t gelu, void* yv, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    if (S < 0 || C <= 0 || K < 1 || K > kC0MaxK || stride < 1 || !x || !w || !yv) return WX_E_INVALID;
+    typename C0Out<OT>::type* y = static_cast<typename C0Out<OT>::type*>(yv);
     const int64_t L = S >= K ? (S - K) / stride + 1 : 0;
     if (L == 0) return WX_OK;
     if (!workspace || workspace_bytes < wx_conv0_channel_norm_workspace_bytes(L, C)) return WX_E_WORKSPACE;
@@ -930,7 +1017,7 @@ extern "C" int wx_conv0_channel_norm(const float* x, int64_t S, int32_t K, int32
         hipLaunchKernelGGL((conv0_stats_rl_kernel<10, 5>), grid, dim3(256), 0, st, x, S, L, w, C, part);
         hipLaunchKernelGGL(conv0_finish_kernel, dim3((C + kCols - 1) / kCols), dim3(kCols * kRows), 0, st, part,
                            (int)nblk, L, C, gamma, beta, eps, ab);
-        hipLaunchKernelGGL((conv0_apply_rl_kernel<10, 5>), grid, dim3(256), 0, st, x, S, L, w, C, ab, gelu, y);
+        hipLaunchKernelGGL((conv0_apply_rl_kernel<10, 5, OT>), grid, dim3(256), 0, st, x, S, L, w, C, ab, gelu, y);
         return wx::launch_status();
     }
     const dim3 grid((C + kCols - 1) / kCols, (unsigned)nblk), blk(kCols * kRows);
@@ -939,7 +1026,7 @@ extern "C" int wx_conv0_channel_norm(const float* x, int64_t S, int32_t K, int32
         hipLaunchKernelGGL(conv0_stats_kernel<KK>, grid, blk, 0, st, x, L, stride, w, C, part);           \
         hipLaunchKernelGGL(conv0_finish_kernel, dim3((C + kCols - 1) / kCols), blk, 0, st, part, (int)nblk, L, C, \
                            gamma, beta, eps, ab);                                                              \
-        hipLaunchKernelGGL(conv0_apply_kernel<KK>, grid, blk, 0, st, x, L, stride, w, C, ab, gelu, y);    \
+        hipLaunchKernelGGL((conv0_apply_kernel<KK, OT>), grid, blk, 0, st, x, L, stride, w, C, ab, gelu, y); \
         break;
     switch (K) {
         WX_C0(1) WX_C0(2) WX_C0(3) WX_C0(4) WX_C0(5) WX_C0(6) WX_C0(7) WX_C0(8) WX_C0(9) WX_C0(10) WX_C0(11)
@@ -948,6 +1035,30 @@ extern "C" int wx_conv0_channel_norm(const float* x, int64_t S, int32_t K, int32
     }
 #undef WX_C0
     return wx::launch_status();
+}
+
+}  // namespace wxe
+
+extern "C" int wx_conv0_channel_norm(const float* x, int64_t S, int32_t K, int32_t stride, const float* w,
+                                     const float* bias, int32_t C, const float* gamma, const float* beta, float eps,
+                                     int32_t gelu, float* y, void* workspace, size_t workspace_bytes, void* stream) {
+    (void)bias;  // cancels in the per-channel normalisation (see above): never added
+    return wxe::conv0_channel_norm<0>(x, S, K, stride, w, C, gamma, beta, eps, gelu, y, workspace, workspace_bytes,
+                                      stream);
+}
+
+extern "C" int wx_conv0_channel_norm_h16(const float* x, int64_t S, int32_t K, int32_t stride, const float* w,
+                                         const float* bias, int32_t C, const float* gamma, const float* beta, float eps,
+                                         int32_t gelu, int32_t dtype, void* y, void* workspace, size_t workspace_bytes,
+                                         void* stream) {
+    (void)bias;
+    if (dtype == WX_DTYPE_F16)
+        return wxe::conv0_channel_norm<WX_DTYPE_F16>(x, S, K, stride, w, C, gamma, beta, eps, gelu, y, workspace,
+                                                     workspace_bytes, stream);
+    if (dtype == WX_DTYPE_BF16)
+        return wxe::conv0_channel_norm<WX_DTYPE_BF16>(x, S, K, stride, w, C, gamma, beta, eps, gelu, y, workspace,
+                                                      workspace_bytes, stream);
+    return WX_E_INVALID;
 }
 
 extern "C" int wx_attention_f32(const float* q, const float* k, const float* v, float* o, int32_t B, int32_t H,
@@ -1100,6 +1211,45 @@ extern "C" int wx_add_layernorm_h16(const float* a, const void* b, int64_t rows,
     }
 #undef WX_LN16_D
 #undef WX_LN16
+    return wx::launch_status();
+}
+
+extern "C" int wx_add_layernorm_h16_dual(const float* a, const void* b, int64_t rows, int32_t D, int64_t a_stride,
+                                         int64_t b_stride, const float* gamma, const float* beta, float eps,
+                                         int32_t dtype, float* y32, void* y16, float* sum_out, void* stream) {
+    using namespace wxe;
+    if (rows < 0 || (D != 768 && D != 1024 && D != 512 && D != 256 && D != 384 && D != 1280) ||
+        (dtype != WX_DTYPE_F16 && dtype != WX_DTYPE_BF16))
+        return WX_E_INVALID;
+    if (rows == 0) return WX_OK;  // (an empty tensor may have no storage)
+    if (!a || !gamma || !beta || !y16) return WX_E_INVALID;
+    if (a_stride < D || (a_stride & 3) || (b && (b_stride < D || (b_stride & 7)))) return WX_E_INVALID;
+    for (const void* p : {(const void*)a, b, (const void*)gamma, (const void*)beta, (const void*)y32, (const void*)y16,
+                          (const void*)sum_out})
+        if (reinterpret_cast<uintptr_t>(p) & 15) return WX_E_INVALID;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    const unsigned short* bh = static_cast<const unsigned short*>(b);
+    unsigned short* yh = static_cast<unsigned short*>(y16);
+#define WX_LND(BF, ...)                                                                                          \
+    hipLaunchKernelGGL((add_ln_dual_kernel<BF, __VA_ARGS__>), grid, dim3(256), 0, st, a, bh, gamma, beta, eps, rows, \
+                       a_stride, b_stride, (int64_t)D, y32, yh, sum_out)
+#define WX_LND_D(BF)                             \
+    switch (D) {                                 \
+        case 256: WX_LND(BF, 1); break;          \
+        case 512: WX_LND(BF, 2); break;          \
+        case 768: WX_LND(BF, 3); break;          \
+        case 384: WX_LND(BF, 2, 96); break;      \
+        case 1280: WX_LND(BF, 5); break;         \
+        default: WX_LND(BF, 4); break;           \
+    }
+    if (dtype == WX_DTYPE_BF16) {
+        WX_LND_D(true)
+    } else {
+        WX_LND_D(false)
+    }
+#undef WX_LND_D
+#undef WX_LND
     return wx::launch_status();
 }
 
