@@ -1,8 +1,8 @@
 """WhisperDecoder without a GPU: the accepted weight forms and the refusals, the host route
 against transformers' decoder (fp64 as the reference, 4 x the stock fp32 route's own error as the
-bound; greedy decoding token for token against the fp64 greedy loop), the limits, and
-wx_decode_attention_f32's argument validation (no device needed: it returns before anything is
-enqueued)."""
+bound; greedy decoding token for token against the fp64 greedy loop), the limits, and the four
+wx_decode_attention_* entry points' argument validation (no device needed: they return before
+anything is enqueued)."""
 import ctypes
 
 import pytest
@@ -143,30 +143,51 @@ def test_limits():
     assert max(len(r) for r in dec.generate(c.enc, PROMPT, 95, max_length=448)) <= 40 - 3
 
 
-def test_decode_attention_entry_validates_before_anything_is_enqueued():
-    """No device: every case returns before a launch (dummy, aligned, never dereferenced pointers)."""
+@pytest.mark.parametrize("half", [False, True], ids=["f32", "h16"])
+@pytest.mark.parametrize("grouped", [False, True], ids=["ungrouped", "grouped"])
+def test_decode_attention_entry_validates_before_anything_is_enqueued(half, grouped):
+    """No device: every case of every entry point returns before a launch (dummy, aligned, never
+    dereferenced pointers).  One table for the four: the grouped forms take G and three q strides,
+    the half forms a dtype and strides in multiples of 8."""
     from whisperx_amd import _lib
 
     lib = _lib.load(require_device=False)
+    fn = getattr(lib, f"wx_decode_attention_{'h16' if half else 'f32'}{'_grouped' if grouped else ''}")
     p = ctypes.c_void_p(1 << 20)
-    qs, ks = (ctypes.c_int64 * 2)(6 * 64, 64), (ctypes.c_int64 * 3)(6 * 448 * 64, 448 * 64, 64)
+    qs = (ctypes.c_int64 * 3)(5 * 6 * 64, 6 * 64, 64) if grouped else (ctypes.c_int64 * 2)(6 * 64, 64)
+    ks = (ctypes.c_int64 * 3)(6 * 448 * 64, 448 * 64, 64)
 
-    def call(B=2, H=6, L=300, D=64, ws=None, q=p, o=p, k_strides=ks):
-        need = lib.wx_decode_attention_workspace_bytes(B, H, L)
-        return lib.wx_decode_attention_f32(q, p, p, o, B, H, L, D, qs, k_strides, ks, 0.125, p,
-                                           need if ws is None else ws, None)
+    def needed(B, G, H, L):
+        if grouped:
+            return lib.wx_decode_attention_grouped_workspace_bytes(B, G, H, L)
+        return lib.wx_decode_attention_workspace_bytes(B, H, L)
+
+    def call(B=2, G=5, H=6, L=300, D=64, ws=None, q=p, o=p, q_strides=qs, k_strides=ks, dtype=1):
+        dims = (B, G, H, L, D) if grouped else (B, H, L, D)
+        return fn(q, p, p, o, *dims, q_strides, k_strides, ks, 0.125, *((dtype,) if half else ()), p,
+                  needed(B, G, H, L) if ws is None else ws, None)
 
     assert call(D=32) == 1001 and call(L=0) == 1001 and call(B=-1) == 1001 and call(H=0) == 1001
     assert call(B=0) == 0 and call(B=0, ws=0) == 0
     assert call(B=0, D=32) == 1001  # the shape is judged first
+    if grouped:  # G outside 1 .. 8, before B == 0
+        assert call(G=0) == 1001 and call(G=9) == 1001 and call(B=0, G=0) == 1001 and call(B=0, G=9) == 1001
+        assert call(B=0, G=1) == 0 and call(B=0, G=8) == 0
+    if half:  # a dtype that is neither fp16 nor bf16, before B == 0
+        assert call(dtype=0) == 1001 and call(dtype=3) == 1001 and call(B=0, dtype=0) == 1001 and call(B=0, dtype=3) == 1001
+        assert call(B=0, dtype=2) == 0
     assert call(q=None) == 1001 and call(o=ctypes.c_void_p((1 << 20) + 4)) == 1001
     assert call(k_strides=(ctypes.c_int64 * 3)(6 * 448 * 64, 448 * 64, 66)) == 1001  # rows off 16 bytes
+    assert call(q_strides=(ctypes.c_int64 * 3)(5 * 6 * 64, 6 * 64 + 2, 64)) == 1001
+    if half:  # 16 bytes are 8 elements: a multiple of 4 is not enough
+        assert call(k_strides=(ctypes.c_int64 * 3)(6 * 448 * 64, 448 * 64, 68)) == 1001
+        assert call(q_strides=(ctypes.c_int64 * 3)(5 * 6 * 64 + 4, 6 * 64, 64)) == 1001
     assert call(B=70000) == 1001
-    need = lib.wx_decode_attention_workspace_bytes(2, 6, 300)
+    need = needed(2, 5, 6, 300)
     assert call(ws=need - 1) == 1004
+    assert need >= 2 * (5 if grouped else 1) * 6 * 3 * 66 * 4  # (m, l, acc[64]) per chunk
     wsb = lib.wx_decode_attention_workspace_bytes
     assert wsb(1, 1, 1) > 0
-    assert need >= 2 * 6 * 3 * 66 * 4  # (m, l, acc[64]) per chunk
     assert wsb(1, 6, 1500) < wsb(2, 6, 1500) < wsb(16, 6, 1500)
     assert wsb(2, 6, 1) <= wsb(2, 6, 448) < wsb(2, 6, 1500) < wsb(2, 6, 30000)
     assert _lib.DECODE_CHUNK == 128 and wsb(1, 1, 128) == wsb(1, 1, 1) < wsb(1, 1, 129 + 128 * 64)

@@ -26,8 +26,7 @@ SRC_PATHS = [SRC_PATH, os.path.join(_HERE, "csrc", "wx_binarize.hip"), os.path.j
              os.path.join(_HERE, "csrc", "wx_vad.hip"), os.path.join(_HERE, "csrc", "wx_diarize.hip"),
              os.path.join(_HERE, "csrc", "wx_mel.hip"), os.path.join(_HERE, "csrc", "wx_whisper.hip"),
              os.path.join(_HERE, "csrc", "wx_decode.hip"), os.path.join(_HERE, "csrc", "wx_beam.hip"),
-             os.path.join(_HERE, "csrc", "wx_attention_h16.hip"), os.path.join(_HERE, "csrc", "wx_decode_h16.hip"),
-             os.path.join(_HERE, "csrc", "wx_prefill.hip")]
+             os.path.join(_HERE, "csrc", "wx_attention_h16.hip"), os.path.join(_HERE, "csrc", "wx_prefill.hip")]
 INST_PATH = os.path.join(_HERE, "csrc", "wx_align_inst.hip")
 HDR_PATHS = sorted(glob.glob(os.path.join(_HERE, "csrc", "*.h"))) + [INST_PATH]  # (a new header: a rebuild)
 INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
@@ -759,33 +758,7 @@ def decode_attention_f32(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scal
     stride with a contiguous head dim and 16-byte aligned rows, read in place (the self-attention
     cache, or the halves of the cross-attention [B, P, 2 H 64] GEMM output).  Returns [B, H, 64]
     contiguous (`out` when given) on the current stream."""
-    lib = load()
-    if q.dim() != 3 or k.dim() != 4 or v.dim() != 4:
-        raise WXError(f"decode_attention_f32: q {tuple(q.shape)} / k {tuple(k.shape)} / v {tuple(v.shape)} are not "
-                      "[B, H, 64] / [B, H, Lcap, 64] / [B, H, Lcap, 64]")
-    B, H, D = (int(x) for x in q.shape)
-    Lcap = int(k.shape[2])
-    L = Lcap if L is None else int(L)
-    if tuple(k.shape) != (B, H, Lcap, D) or tuple(v.shape) != (B, H, Lcap, D) or not 1 <= L <= Lcap:
-        raise WXError(f"decode_attention_f32: k {tuple(k.shape)} / v {tuple(v.shape)} do not hold {L} rows for q "
-                      f"{tuple(q.shape)}")
-    dev = q.device
-    for t in (q, k, v):
-        if t.dtype != torch.float32 or not t.is_cuda or t.device != dev or t.stride(-1) != 1:
-            raise WXError("decode_attention_f32: q, k and v must be float32 tensors on one HIP device with a contiguous "
-                          "head dim")
-    if out is None:
-        out = torch.empty((B, H, D), dtype=torch.float32, device=dev)
-    if tuple(out.shape) != (B, H, D) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
-        raise WXError("decode_attention_f32: out must be a contiguous float32 [B, H, 64] tensor on the queries' device")
-    st = [(ctypes.c_int64 * n)(*(int(x) for x in t.stride()[:n])) for t, n in ((q, 2), (k, 3), (v, 3))]
-    wsb = lib.wx_decode_attention_workspace_bytes(B, H, L)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev)
-        ws = _scratch.get("decode_attention", dev, wsb, stream)
-        _check(lib.wx_decode_attention_f32(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, H, L, D, st[0], st[1], st[2],
-                                           float(scale), _ptr(ws), ws.numel(), ctypes.c_void_p(stream.cuda_stream)))
-    return out
+    return _decode_attention("decode_attention_f32", q, k, v, scale, L, out, False, False)
 
 
 DECODE_MAX_GROUP = 8  # WX_DECODE_ATTENTION_MAX_GROUP: queries per (batch, head) of the grouped kernel
@@ -799,35 +772,7 @@ def decode_attention_f32_grouped(q: torch.Tensor, k: torch.Tensor, v: torch.Tens
     under decode_attention_f32's stride and alignment rules.  Returns [B, G, H, 64] contiguous
     (`out` when given) on the current stream; row (b, g, h) has the bits decode_attention_f32
     gives that query on the same k / v."""
-    lib = load()
-    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
-        raise WXError(f"decode_attention_f32_grouped: q {tuple(q.shape)} / k {tuple(k.shape)} / v {tuple(v.shape)} "
-                      "are not [B, G, H, 64] / [B, H, Lcap, 64] / [B, H, Lcap, 64]")
-    B, G, H, D = (int(x) for x in q.shape)
-    Lcap = int(k.shape[2])
-    L = Lcap if L is None else int(L)
-    if tuple(k.shape) != (B, H, Lcap, D) or tuple(v.shape) != (B, H, Lcap, D) or not 1 <= L <= Lcap:
-        raise WXError(f"decode_attention_f32_grouped: k {tuple(k.shape)} / v {tuple(v.shape)} do not hold {L} rows "
-                      f"for q {tuple(q.shape)}")
-    dev = q.device
-    for t in (q, k, v):
-        if t.dtype != torch.float32 or not t.is_cuda or t.device != dev or t.stride(-1) != 1:
-            raise WXError("decode_attention_f32_grouped: q, k and v must be float32 tensors on one HIP device with a "
-                          "contiguous head dim")
-    if out is None:
-        out = torch.empty((B, G, H, D), dtype=torch.float32, device=dev)
-    if tuple(out.shape) != (B, G, H, D) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
-        raise WXError("decode_attention_f32_grouped: out must be a contiguous float32 [B, G, H, 64] tensor on the "
-                      "queries' device")
-    st = [(ctypes.c_int64 * 3)(*(int(x) for x in t.stride()[:3])) for t in (q, k, v)]
-    wsb = lib.wx_decode_attention_grouped_workspace_bytes(B, G, H, L)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev)
-        ws = _scratch.get("decode_attention_grouped", dev, wsb, stream)
-        _check(lib.wx_decode_attention_f32_grouped(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, G, H, L, D, st[0], st[1],
-                                                   st[2], float(scale), _ptr(ws), ws.numel(),
-                                                   ctypes.c_void_p(stream.cuda_stream)))
-    return out
+    return _decode_attention("decode_attention_f32_grouped", q, k, v, scale, L, out, False, True)
 
 
 def beam_topk(logits: torch.Tensor, cum: torch.Tensor, G: int):
@@ -1057,9 +1002,9 @@ def add_layernorm_h16(a: torch.Tensor, b: Optional[torch.Tensor], gamma: torch.T
     return (y, s) if want_sum else y
 
 
-def _decode_attention_h16(who: str, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, L: Optional[int],
-                          out: Optional[torch.Tensor], grouped: bool) -> torch.Tensor:
-    """decode_attention_h16 (q [B, H, 64]) and decode_attention_h16_grouped (q [B, G, H, 64])."""
+def _decode_attention(who: str, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, L: Optional[int],
+                      out: Optional[torch.Tensor], half: bool, grouped: bool) -> torch.Tensor:
+    """decode_attention_f32 / _h16 (q [B, H, 64]) and their _grouped forms (q [B, G, H, 64])."""
     lib = load()
     qd = 4 if grouped else 3
     lead = "[B, G, H, 64]" if grouped else "[B, H, 64]"
@@ -1072,30 +1017,25 @@ def _decode_attention_h16(who: str, q: torch.Tensor, k: torch.Tensor, v: torch.T
     if tuple(k.shape) != (B, H, Lcap, D) or tuple(v.shape) != (B, H, Lcap, D) or not 1 <= L <= Lcap:
         raise WXError(f"{who}: k {tuple(k.shape)} / v {tuple(v.shape)} do not hold {L} rows for q {tuple(q.shape)}")
     dev = q.device
-    code = HALF_DTYPES.get(q.dtype)
+    code = HALF_DTYPES.get(q.dtype) if half else None
     for t in (q, k, v):
-        if code is None or t.dtype != q.dtype or not t.is_cuda or t.device != dev or t.stride(-1) != 1:
-            raise WXError(f"{who}: q, k and v must share one of float16 / bfloat16, on one HIP device with a contiguous "
-                          "head dim")
+        if (code is None if half else t.dtype != torch.float32) or t.dtype != q.dtype or not t.is_cuda or \
+                t.device != dev or t.stride(-1) != 1:
+            raise WXError(f"{who}: q, k and v must {'share one of float16 / bfloat16' if half else 'be float32 tensors'}, "
+                          "on one HIP device with a contiguous head dim")
     if out is None:
         out = torch.empty(tuple(q.shape), dtype=q.dtype, device=dev)
     if tuple(out.shape) != tuple(q.shape) or out.dtype != q.dtype or out.device != dev or not out.is_contiguous():
         raise WXError(f"{who}: out must be a contiguous {lead} tensor of the queries' dtype on their device")
     st = [(ctypes.c_int64 * n)(*(int(x) for x in t.stride()[:n])) for t, n in ((q, qd - 1), (k, 3), (v, 3))]
+    dims = (B, int(q.shape[1]), H, L) if grouped else (B, H, L)
+    name = "decode_attention_grouped" if grouped else "decode_attention"
+    fn = getattr(lib, f"wx_decode_attention_{'h16' if half else 'f32'}{'_grouped' if grouped else ''}")
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
-        if grouped:
-            G = int(q.shape[1])
-            ws = _scratch.get("decode_attention_grouped", dev, lib.wx_decode_attention_grouped_workspace_bytes(B, G, H, L),
-                              stream)
-            _check(lib.wx_decode_attention_h16_grouped(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, G, H, L, D, st[0], st[1],
-                                                       st[2], float(scale), code, _ptr(ws), ws.numel(),
-                                                       ctypes.c_void_p(stream.cuda_stream)))
-        else:
-            ws = _scratch.get("decode_attention", dev, lib.wx_decode_attention_workspace_bytes(B, H, L), stream)
-            _check(lib.wx_decode_attention_h16(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, H, L, D, st[0], st[1], st[2],
-                                               float(scale), code, _ptr(ws), ws.numel(),
-                                               ctypes.c_void_p(stream.cuda_stream)))
+        ws = _scratch.get(name, dev, getattr(lib, f"wx_{name}_workspace_bytes")(*dims), stream)
+        _check(fn(_ptr(q), _ptr(k), _ptr(v), _ptr(out), *dims, D, st[0], st[1], st[2], float(scale),
+                  *((code,) if half else ()), _ptr(ws), ws.numel(), ctypes.c_void_p(stream.cuda_stream)))
     return out
 
 
@@ -1106,7 +1046,7 @@ def decode_attention_h16(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scal
     every other stride a multiple of 8 elements, 16-byte aligned).  Returns [B, H, 64] contiguous in
     that dtype (`out` when given) on the current stream: decode_attention_f32 of the widened inputs,
     rounded once."""
-    return _decode_attention_h16("decode_attention_h16", q, k, v, scale, L, out, False)
+    return _decode_attention("decode_attention_h16", q, k, v, scale, L, out, True, False)
 
 
 def decode_attention_h16_grouped(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float,
@@ -1115,7 +1055,7 @@ def decode_attention_h16_grouped(q: torch.Tensor, k: torch.Tensor, v: torch.Tens
     against the k / v [B, H, Lcap, 64] they share, under decode_attention_h16's rules.  Returns
     [B, G, H, 64] contiguous in that dtype; row (b, g, h) has the bits decode_attention_h16 gives that
     query on the same k / v."""
-    return _decode_attention_h16("decode_attention_h16_grouped", q, k, v, scale, L, out, True)
+    return _decode_attention("decode_attention_h16_grouped", q, k, v, scale, L, out, True, True)
 
 
 def _prefill_attention(who: str, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, causal: Optional[int],

@@ -37,7 +37,9 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "wx_half.h"
 #include "wx_host.h"  // (and through it include/wx_align.h)
+#include "wx_wave.h"
 
 namespace wxh {
 
@@ -63,17 +65,7 @@ struct AttnH16Args {
     float scale_log2;                                      // softmax scale * log2(e)
 };
 
-// BF: bf16 (else fp16).  Bit patterns travel as shorts; round() is round-to-nearest-even.
-template <bool BF>
-__device__ __forceinline__ short round16(float x) {
-    if constexpr (BF) return __builtin_bit_cast(short, (__bf16)x);
-    else return __builtin_bit_cast(short, (_Float16)x);
-}
-template <bool BF>
-__device__ __forceinline__ float widen16(short x) {
-    if constexpr (BF) return __uint_as_float((unsigned)(unsigned short)x << 16);
-    else return (float)__builtin_bit_cast(_Float16, x);
-}
+// BF: bf16 (else fp16).  Bit patterns travel as shorts (wx_half.h).
 template <bool BF>
 __device__ __forceinline__ f32x16 mfma16(s16x8 a, s16x8 b, f32x16 c) {
     if constexpr (BF)
@@ -97,6 +89,7 @@ template <bool BF>
 __device__ __forceinline__ void attn_h16_unit(const short* Q, const short* K, const short* V, short* O, const int T,
                                               const int tile, const int64_t sqt, const int64_t skt, const int64_t svt,
                                               const int64_t orow, const float scale_log2, char* lds) {
+    constexpr int ET = wx::half_et(BF);
     const int q0 = tile * kQueries;
     const int l = threadIdx.x & 63, r = l & 31, hf = l >> 5;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (uniform, which hipcc cannot prove)
@@ -192,9 +185,9 @@ __device__ __forceinline__ void attn_h16_unit(const short* Q, const short* K, co
             float ps = 0.f;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const short ph = round16<BF>(__builtin_amdgcn_exp2f(s[u][i] - mn));
+                const short ph = wx::round16<ET>(__builtin_amdgcn_exp2f(s[u][i] - mn));
                 pf[u][i >> 3][i & 7] = ph;
-                ps += widen16<BF>(ph);
+                ps += wx::widen16<ET>(ph);
             }
             ps += __shfl_xor(ps, 32);
             lsum[u] = lsum[u] * alpha + ps;
@@ -283,21 +276,13 @@ __device__ __forceinline__ void attn_h16_unit(const short* Q, const short* K, co
             s16x4 x0, x1;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                x0[j] = round16<BF>(o0[u][4 * g + j] * inv);
-                x1[j] = round16<BF>(o1[u][4 * g + j] * inv);
+                x0[j] = wx::round16<ET>(o0[u][4 * g + j] * inv);
+                x1[j] = wx::round16<ET>(o1[u][4 * g + j] * inv);
             }
             *reinterpret_cast<s16x4*>(orow_p + d) = x0;
             *reinterpret_cast<s16x4*>(orow_p + 32 + d) = x1;
         }
     }
-}
-
-
-// 1-D grid, block L runs on XCD L % 8: hand each XCD a contiguous run of (head, query tile)
-// units, so the blocks sharing one head's K / V meet in one XCD's L2 (as attn_f32_kernel)
-__device__ __forceinline__ unsigned xcd_unit() {
-    const unsigned L = blockIdx.x, n = gridDim.x, x = L % 8, i = L / 8, q = n / 8, r = n % 8;
-    return x * q + min(x, r) + i;
 }
 
 // amdgpu_waves_per_eu(2): 223 VGPRs, no spill.  With one query tile per wave (141 VGPRs) two, three
@@ -309,7 +294,7 @@ template <bool BF>
 __global__ __launch_bounds__(64 * kSplit) __attribute__((amdgpu_waves_per_eu(2))) void attn_h16_kernel(AttnH16Args a) {
     __shared__ __attribute__((aligned(16))) char lds[kLdsBytes];
     const int T = a.T;
-    const unsigned w = xcd_unit();
+    const unsigned w = wx::xcd_unit();  // (head, query tile) units
     const int nq = (T + kQueries - 1) / kQueries;
     const int tile = (int)(w % (unsigned)nq);
     const int bh = (int)(w / (unsigned)nq);
@@ -336,7 +321,7 @@ template <bool BF>
 __global__ __launch_bounds__(64 * kSplit) __attribute__((amdgpu_waves_per_eu(2))) void attn_h16_packed_kernel(
     AttnH16PackedArgs a) {
     __shared__ __attribute__((aligned(16))) char lds[kLdsBytes];
-    const unsigned w = xcd_unit();
+    const unsigned w = wx::xcd_unit();  // (head, query tile) units
     // the segment owning unit w: the last s with seg_units[s] <= w (an empty segment owns no unit,
     // so the last such s is never one of them: T >= 1 below)
     int lo = 0, hi = a.nseg - 1;

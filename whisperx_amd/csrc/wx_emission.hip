@@ -12,7 +12,9 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "wx_half.h"
 #include "wx_host.h"  // (and through it include/wx_align.h)
+#include "wx_wave.h"
 
 namespace wxe {
 
@@ -417,14 +419,7 @@ __global__ __launch_bounds__(64 * SPLIT) __attribute__((amdgpu_waves_per_eu(2)))
     int T, tile, h;
     int64_t row0;  // o row of query 0 of this batch entry / segment
     const float *Q, *K, *V;
-    // 1-D grid, block L runs on XCD L % 8 (round-robin dispatch): hand each XCD a contiguous
-    // run of (head, query tile) units, so the blocks sharing one head's K / V (768 KB at
-    // T = 1499) meet in one XCD's L2 instead of all eight
-    // (round 4 A/B: the plain blockIdx order was 1-2% slower)
-    const unsigned w = [] {
-        const unsigned L = blockIdx.x, n = gridDim.x, x = L % 8, i = L / 8, q = n / 8, r = n % 8;
-        return x * q + min(x, r) + i;
-    }();
+    const unsigned w = wx::xcd_unit();  // (head, query tile) units
     if (PACKED) {
         // the segment owning unit w: the last s with seg_units[s] <= w (empty segments own no
         // units, so the last such s is never one of them)
@@ -674,17 +669,6 @@ __global__ __launch_bounds__(256) void add_ln_kernel(const float* __restrict__ a
 // zeros, added like any other, so that the result is add_ln_kernel's on a zero b), y is rounded
 // to nearest even on the store, the sum stays fp32.  Everything between is add_ln_kernel's,
 // expression for expression: y is bit for bit the rounding of its y.
-template <bool BF>
-__device__ __forceinline__ float ln_widen16(unsigned short x) {
-    if constexpr (BF) return __uint_as_float((unsigned)x << 16);
-    else return (float)__builtin_bit_cast(_Float16, x);
-}
-template <bool BF>
-__device__ __forceinline__ unsigned short ln_round16(float x) {
-    if constexpr (BF) return __builtin_bit_cast(unsigned short, (__bf16)x);
-    else return __builtin_bit_cast(unsigned short, (_Float16)x);
-}
-
 template <bool BF, int NV, int D4 = 64 * NV>
 __global__ __launch_bounds__(256) void add_ln_h16_kernel(const float* __restrict__ a, const unsigned short* __restrict__ b,
                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -693,7 +677,7 @@ __global__ __launch_bounds__(256) void add_ln_h16_kernel(const float* __restrict
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const int l = threadIdx.x & 63;
-    constexpr int D = 4 * D4;
+    constexpr int D = 4 * D4, ET = wx::half_et(BF);
     constexpr bool kFull = D4 == 64 * NV;
     static_assert(D4 <= 64 * NV && D4 > 64 * (NV - 1), "NV float4 per lane cover the row");
     const float4* pa = reinterpret_cast<const float4*>(a + row * sa);
@@ -710,7 +694,7 @@ __global__ __launch_bounds__(256) void add_ln_h16_kernel(const float* __restrict
         float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
         if (pb) {
             const ushort4 u = pb[64 * i + l];
-            z = make_float4(ln_widen16<BF>(u.x), ln_widen16<BF>(u.y), ln_widen16<BF>(u.z), ln_widen16<BF>(u.w));
+            z = make_float4(wx::widen16<ET>(u.x), wx::widen16<ET>(u.y), wx::widen16<ET>(u.z), wx::widen16<ET>(u.w));
         }
         v[i] = make_float4(x.x + z.x, x.y + z.y, x.z + z.z, x.w + z.w);
         acc += (v[i].x + v[i].y) + (v[i].z + v[i].w);
@@ -736,10 +720,10 @@ __global__ __launch_bounds__(256) void add_ln_h16_kernel(const float* __restrict
     for (int i = 0; i < NV; ++i) {
         if (!kFull && 64 * i + l >= D4) continue;
         const float4 g = pg[64 * i + l], t = pt[64 * i + l];
-        py[64 * i + l] = make_ushort4(ln_round16<BF>((v[i].x - mean) * rstd * g.x + t.x),
-                                      ln_round16<BF>((v[i].y - mean) * rstd * g.y + t.y),
-                                      ln_round16<BF>((v[i].z - mean) * rstd * g.z + t.z),
-                                      ln_round16<BF>((v[i].w - mean) * rstd * g.w + t.w));
+        py[64 * i + l] = make_ushort4(wx::round16<ET>((v[i].x - mean) * rstd * g.x + t.x),
+                                      wx::round16<ET>((v[i].y - mean) * rstd * g.y + t.y),
+                                      wx::round16<ET>((v[i].z - mean) * rstd * g.z + t.z),
+                                      wx::round16<ET>((v[i].w - mean) * rstd * g.w + t.w));
         if (ps) ps[64 * i + l] = v[i];
     }
 }
@@ -757,7 +741,7 @@ __global__ __launch_bounds__(256) void add_ln_dual_kernel(const float* __restric
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const int l = threadIdx.x & 63;
-    constexpr int D = 4 * D4;
+    constexpr int D = 4 * D4, ET = wx::half_et(BF);
     constexpr bool kFull = D4 == 64 * NV;
     static_assert(D4 <= 64 * NV && D4 > 64 * (NV - 1), "NV float4 per lane cover the row");
     const float4* pa = reinterpret_cast<const float4*>(a + row * sa);
@@ -774,7 +758,7 @@ __global__ __launch_bounds__(256) void add_ln_dual_kernel(const float* __restric
         float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
         if (pb) {
             const ushort4 u = pb[64 * i + l];
-            z = make_float4(ln_widen16<BF>(u.x), ln_widen16<BF>(u.y), ln_widen16<BF>(u.z), ln_widen16<BF>(u.w));
+            z = make_float4(wx::widen16<ET>(u.x), wx::widen16<ET>(u.y), wx::widen16<ET>(u.z), wx::widen16<ET>(u.w));
         }
         v[i] = make_float4(x.x + z.x, x.y + z.y, x.z + z.z, x.w + z.w);
         acc += (v[i].x + v[i].y) + (v[i].z + v[i].w);
@@ -804,7 +788,7 @@ __global__ __launch_bounds__(256) void add_ln_dual_kernel(const float* __restric
         const float4 y = make_float4((v[i].x - mean) * rstd * g.x + t.x, (v[i].y - mean) * rstd * g.y + t.y,
                                      (v[i].z - mean) * rstd * g.z + t.z, (v[i].w - mean) * rstd * g.w + t.w);
         if (p32) p32[64 * i + l] = y;
-        p16[64 * i + l] = make_ushort4(ln_round16<BF>(y.x), ln_round16<BF>(y.y), ln_round16<BF>(y.z), ln_round16<BF>(y.w));
+        p16[64 * i + l] = make_ushort4(wx::round16<ET>(y.x), wx::round16<ET>(y.y), wx::round16<ET>(y.z), wx::round16<ET>(y.w));
         if (ps) ps[64 * i + l] = v[i];
     }
 }

@@ -27,13 +27,15 @@
 //   - One template over the element type.  fp16 / bf16 elements are widened to fp32 exactly where
 //     the fp32 kernel reads a float, and o is rounded to nearest even once, on the store: the h16
 //     entry is the f32 entry on the widened inputs, rounded, bit for bit (the decoder's half
-//     contract, wx_decode_h16.hip; no packed 16-bit math, no 16-bit MFMA).
+//     contract, wx_decode.hip; no packed 16-bit math, no 16-bit MFMA).
 //
 // Built with -ffp-contract=off -fno-fast-math (whisperx_amd/_lib.py BASE_FLAGS).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "wx_half.h"
 #include "wx_host.h"  // (and through it include/wx_align.h)
+#include "wx_wave.h"
 
 namespace wxpre {
 
@@ -45,7 +47,7 @@ constexpr int kHead = 64;
 constexpr int kSplit = 4;  // waves per 32-query tile, each over every kSplit-th 32-key tile
 constexpr int64_t kMaxRowStride = (int64_t)1 << 23;  // K / V time stride: 32-bit byte offsets within a key tile
 
-enum { kF32 = 0, kF16 = WX_DTYPE_F16, kBF16 = WX_DTYPE_BF16 };
+using wx::kF32, wx::kF16, wx::kBF16, wx::widen16, wx::round16;  // (wx_half.h)
 
 struct PreArgs {
     const void *q, *k, *v;
@@ -54,17 +56,6 @@ struct PreArgs {
     int64_t qs[3], ks[3], vs[3];  // element strides {batch, head, time} (head dim: 1)
     float scale_log2;             // softmax scale * log2(e)
 };
-
-template <int ET>
-__device__ __forceinline__ float widen16(unsigned short x) {
-    if constexpr (ET == kBF16) return __uint_as_float((unsigned)x << 16);
-    else return (float)__builtin_bit_cast(_Float16, x);
-}
-template <int ET>
-__device__ __forceinline__ short round16(float x) {
-    if constexpr (ET == kBF16) return __builtin_bit_cast(short, (__bf16)x);
-    else return __builtin_bit_cast(short, (_Float16)x);
-}
 
 // What a lane holds of one 32-key tile, as loaded (16-bit elements are widened where they are used,
 // so the loads of the next tile stay in flight behind this tile's arithmetic):
@@ -97,12 +88,7 @@ template <int ET>
 __global__ __launch_bounds__(64 * kSplit) __attribute__((amdgpu_waves_per_eu(2))) void prefill_attn_kernel(PreArgs a) {
     constexpr int ES = Tile<ET>::ES;
     typedef typename std::conditional<ET == kF32, float, short>::type elem;
-    // attn_f32_kernel's block order: each XCD a contiguous run of (batch, head, query tile) units,
-    // so the blocks sharing one head's K / V meet in one L2
-    const unsigned w = [] {
-        const unsigned L = blockIdx.x, n = gridDim.x, x = L % 8, i = L / 8, q = n / 8, r = n % 8;
-        return x * q + min(x, r) + i;
-    }();
+    const unsigned w = wx::xcd_unit();  // (batch, head, query tile) units
     const int Tq = a.Tq, Tk = a.Tk, causal = a.causal;
     const int nq = (Tq + 31) / 32;
     const int tile = (int)(w % (unsigned)nq);
