@@ -9,7 +9,7 @@ launch ends with its slowest segment.  This tool builds the decision bits of syn
 segment tops a walker enters on another column, for guesses moved off the straight line
 (0, 0)-(T, N) by a constant or by k (T - 2 N) / T columns.
 
-    python tools/walk_guess_sim.py [--segments 256]
+    python tools/walk_guess_sim.py [--segments 256] [--waves 8]
 """
 import argparse
 
@@ -72,14 +72,14 @@ RULES = {"line": lambda T, N: 0, "+4": lambda T, N: 4 * T, "+8": lambda T, N: 8 
          "24 (T-2N)/T": lambda T, N: 24 * (T - 2 * N)}
 
 
-def sweep(name, shapes, seed):
+def sweep(name, shapes, seed, waves):
     rng = np.random.default_rng(seed)
     res = {r: [0, 0, 0, 0] for r in RULES}  # segments with a miss, tops missed, tops, blocks wave 0 walks again
     for T, n_lo, n_hi in shapes:
         em, tk = segment(rng, T, n_lo, n_hi)
         N = len(tk)
         D, ts = decisions(em, tk)
-        K, lo = plan(T)
+        K, lo = plan(T, waves)
         true_at, j = {}, N
         for t in range(ts, 0, -1):
             if t % 32 == 0:
@@ -114,14 +114,16 @@ def sweep(name, shapes, seed):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--segments", type=int, default=256)
-    n = ap.parse_args().segments
-    sweep("config 2 (T 1499, N 300-500)", [(1499, 300, 500)] * n, 1)
-    sweep("sparse (T 1499, N 170-280)", [(1499, 170, 280)] * (n // 2), 2)
-    sweep("dense (T 1499, N 500-544)", [(1499, 500, 544)] * (n // 2), 3)
+    ap.add_argument("--waves", type=int, default=8, help="waves of the split workgroup (walk_spec's K <= waves)")
+    args = ap.parse_args()
+    n, waves = args.segments, args.waves
+    sweep("config 2 (T 1499, N 300-500)", [(1499, 300, 500)] * n, 1, waves)
+    sweep("sparse (T 1499, N 170-280)", [(1499, 170, 280)] * (n // 2), 2, waves)
+    sweep("dense (T 1499, N 500-544)", [(1499, 500, 544)] * (n // 2), 3, waves)
     rr = np.random.default_rng(4321)
     Ts = [int(rr.integers(100, 1500)) for _ in range(3 * n // 4)]
-    sweep("ragged (T 100-1499, N T/6-T/3)", [(T, max(2, T // 6), max(3, T // 3)) for T in Ts], 4)
-    sweep("T 2999, N 850-951", [(2999, 850, 951)] * (n // 5), 5)
+    sweep("ragged (T 100-1499, N T/6-T/3)", [(T, max(2, T // 6), max(3, T // 3)) for T in Ts], 4, waves)
+    sweep("T 2999, N 850-951", [(2999, 850, 951)] * (n // 5), 5, waves)
 
 
 if __name__ == "__main__":

@@ -109,9 +109,14 @@ constexpr int kCkSlots = (W == 1 || VS == 32) ? 2 * W : W;
 
 // Split kernels: waves per workgroup.  Beyond the W DP waves and the two helpers, the rest
 // only keep the forward's barrier count and then walk speculative segments (walk_spec: more
-// walkers, shorter segments).  177 VGPRs allow two waves per SIMD: 8 (12 waves = 168 VGPRs
-// spilled 33 in the register-resident forward).  (6 waves, no extra walkers: config 2
-// 51.4 -> 53.3 us in round 5.)
+// walkers, shorter segments).  Eight, two per SIMD.  Registers no longer decide this: with the
+// blank operand kept once per lane quad (Forward::RegOps) the DP waves' chunk code peaks at
+// v126, and the kernel's 176 VGPRs are col0_helper's two sets of 32 doubles alone; with one
+// set the register-resident kernels need 127 and twelve waves fit without a spill.  Built
+// and measured in round 10: twelve waves (walk_spec's K = 11 on config 2)
+// were 1.1 us slower than eight — every chunk barrier waits for twelve waves, and wave 0's
+// chain through eleven walkers' records after the walk's barrier took back what the shorter
+// segments gave.  (6 waves, no extra walkers: config 2 51.4 -> 53.3 us in round 5.)
 constexpr int kSplitWaves = 8;
 constexpr int kQ0LdsFrames = 4096;  // Split::q0l rows (longer segments: fill_q0 after the walk)
 

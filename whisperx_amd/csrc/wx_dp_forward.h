@@ -18,8 +18,8 @@ using cellvec = float __attribute__((ext_vector_type(C)));
 // Quad-interleaved staging (the register-resident forward, Forward::kReg).  A chunk's 32 rows
 // are kept as 8 row quads; quad p holds, per column c, the 4 values em[4p..4p+3, c] in 16
 // contiguous bytes: float index p * QS + 4 c + (row & 3), QS = 4 (VS + 1).  One 16-byte LDS
-// read then gives a lane 4 steps of its token's column (and, read at a uniform address, 4
-// steps of the blank), instead of one or two dwords per step.  Column VS of each quad is not
+// read then gives a lane 4 steps of its token's column (and a quarter of the lanes 4
+// steps of the blank: RegOps), instead of one or two dwords per step.  Column VS of each quad is not
 // staged: the column-0 helper writes the column-1 wave's lane-0 operand there (see
 // Forward::col0_pre).  The stager fills it from a row-major LDS-DMA ring (Forward::transpose_quads).
 template <int VS>
@@ -287,7 +287,7 @@ struct Forward {
         const bool owner_wave = uniform(own_w) == vw;
         if constexpr (kReg) {  // the register-resident split forward has its own chunk loop
             const int etq = (vw == 0 && l == 0) ? VS * 16 : toff[0] * 4;  // quad byte offset of this lane's column
-            const int ebq = boff * 4;                                      // ... of the blank (uniform)
+            const int ebq = boff * 4 + (l & 3) * kQS * 4;                  // ... of the blank, in this lane's quad of a half-chunk
             reg_forward(sp, lds, xh, bits, cn, nch, T, wv, g, L.G, halo, xpub, xsub, owner, owner_wave, etq, ebq);
             return false;  // (a lost hand-off is the poller's to report: helper_reg)
         }
@@ -467,15 +467,21 @@ struct Forward {
     }
 
     // ---------------------------------------------------------------- register-resident chunks
+    // The blank operand is the same 32 numbers in every lane of a wave, so a lane keeps only a
+    // quarter of them: in half-chunk h (16 steps) lane l holds blank quad 4 h + (l & 3), i.e.
+    // em[16 h + 4 (l & 3) .. + 3, blank], and a step takes its blank from the lane of its own
+    // quad of four lanes that holds it (reg_steps4) — 8 VGPRs per operand set instead of 32, and
+    // one 16-byte LDS read per 16 steps (four addresses per wave) instead of one per 4.
     struct RegOps {
-        float4 et[kChunk / 4];  // em[t, tok] of this lane's cell (column-1 wave, lane 0: col0_pre's value)
-        float4 eb[kChunk / 4];  // em[t, blank]
+        float4 et[kChunk / 4];   // em[t, tok] of this lane's cell (column-1 wave, lane 0: col0_pre's value)
+        float4 eb[kChunk / 16];  // em[t, blank]: blank quad 4 h + (lane & 3) of half-chunk h
     };
+    // ebq: the blank's quad byte offset plus this lane's (l & 3) quads (run()).
     __device__ __forceinline__ static void reg_load(RegOps& o, const char* buf, int etq, int ebq) {
 #pragma unroll
         for (int p = 0; p < kChunk / 4; ++p) {
             o.et[p] = *reinterpret_cast<const float4*>(buf + p * kQS * 4 + etq);
-            o.eb[p] = *reinterpret_cast<const float4*>(buf + p * kQS * 4 + ebq);
+            if (p % 4 == 0) o.eb[p / 4] = *reinterpret_cast<const float4*>(buf + p * kQS * 4 + ebq);
         }
     }
     // Four time steps of one cell (alignment.py:372-378), hand-ordered so that the chain
@@ -487,54 +493,84 @@ struct Forward {
     // col0_pre's tr[t][0] + em[t, tok[0]] (0 + x is x for every x the DP can tell apart: it
     // only compares values and takes maxima), elsewhere a halo lane's don't-care.  n[k] =
     // the cell value after step k.
-#define WX_REG_STEP(CUR, NC, ET, EB)                                                                  \
-    "v_add_f32 %[s], %[" #CUR "], %[" #EB "]\n\t"                                                   \
+    // The stay add takes the blank of step 4 p + k from component k of `eb` as held by lane
+    // R = p % 4 of the lane's quad (quad_perm:[R,R,R,R]; eb + cur is cur + eb bit for bit).  Its
+    // DPP source is an operand register: written by a ds_read (reg_load, reg_chunk) and by
+    // no VALU instruction, so the VALU-write -> DPP-read wait states concern `cur` alone, which
+    // the stay add reads as its plain second source.  quad_perm reads other lanes' registers, which
+    // delivers the value only from active lanes: EXEC is full wherever a DP wave runs these blocks
+    // (every branch of reg_forward around reg_chunk is wave-uniform; its lane-conditional
+    // stores end before the chunk's first block).  Both were checked in the gfx950 code of
+    // <1, 32, 3> and <1, 32, 4>: every quad_perm source is last written by a ds_read_b128, and
+    // no EXEC write or branch stands inside a chunk.
+#define WX_REG_STEP(CUR, NC, ET, EB, R)                                                               \
+    "v_add_f32_dpp %[s], %[" #EB "], %[" #CUR "] quad_perm:[" #R "," #R "," #R "," #R "] row_mask:0xf bank_mask:0xf\n\t" \
     "v_add_f32_dpp %[c], %[" #CUR "], %[" #ET "] wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
     "v_cmp_gt_f32 vcc, %[c], %[s]\n\t"                                                              \
     "v_maximum3_f32 %[" #NC "], %[s], %[c], %[c]\n\t"                                               \
     "v_addc_co_u32 %[w], vcc, %[w], %[w], vcc\n\t"
+#define WX_REG_STEPS4(R)                                                                            \
+    WX_REG_STEP(cur, n0, e0, b0, R) WX_REG_STEP(n0, n1, e1, b1, R) WX_REG_STEP(n1, n2, e2, b2, R)   \
+        WX_REG_STEP(n2, n3, e3, b3, R)
 #define WX_REG_OPERANDS                                                                                 \
     : [n0] "=&v"(n[0]), [n1] "=&v"(n[1]), [n2] "=&v"(n[2]), [n3] "=&v"(n[3]), [w] "+v"(w), [s] "=&v"(s),  \
       [c] "=&v"(c)                                                                                          \
     : [cur] "v"(cur), [e0] "v"(et.x), [e1] "v"(et.y), [e2] "v"(et.z), [e3] "v"(et.w), [b0] "v"(eb.x),     \
       [b1] "v"(eb.y), [b2] "v"(eb.z), [b3] "v"(eb.w)                                                         \
     : "vcc"
-    template <bool FIRST>  // FIRST: `cur` may have just been written by a VALU op (halo copy-in)
+    // FIRST: `cur` may have just been written by a VALU op (halo copy-in); R: the quad lane
+    // holding these four steps' blank
+    template <bool FIRST, int R>
     __device__ __forceinline__ static void reg_steps4(float cur, unsigned& w, const float4& et, const float4& eb,
                                                       float (&n)[4]) {
+        static_assert(0 <= R && R < 4, "quad lane");
         float s, c;
         if constexpr (FIRST)
-            asm volatile("s_nop 1\n\t" WX_REG_STEP(cur, n0, e0, b0) WX_REG_STEP(n0, n1, e1, b1)
-                             WX_REG_STEP(n1, n2, e2, b2) WX_REG_STEP(n2, n3, e3, b3) WX_REG_OPERANDS);
+            asm volatile("s_nop 1\n\t" WX_REG_STEPS4(0) WX_REG_OPERANDS);
+        else if constexpr (R == 0)
+            asm volatile(WX_REG_STEPS4(0) WX_REG_OPERANDS);
+        else if constexpr (R == 1)
+            asm volatile(WX_REG_STEPS4(1) WX_REG_OPERANDS);
+        else if constexpr (R == 2)
+            asm volatile(WX_REG_STEPS4(2) WX_REG_OPERANDS);
         else
-            asm volatile(WX_REG_STEP(cur, n0, e0, b0) WX_REG_STEP(n0, n1, e1, b1) WX_REG_STEP(n1, n2, e2, b2)
-                             WX_REG_STEP(n2, n3, e3, b3) WX_REG_OPERANDS);
+            asm volatile(WX_REG_STEPS4(3) WX_REG_OPERANDS);
+        static_assert(!FIRST || R == 0, "the chunk's first block takes quad lane 0's blank");
     }
 #undef WX_REG_OPERANDS
+#undef WX_REG_STEPS4
 #undef WX_REG_STEP
     // 32 steps on operands `o`, issuing the next chunk's operand reads (n, from buffer nb) one
-    // quad ahead of each group of four steps.  OWN: this wave holds column N (the others have
-    // no column-N code); hist: the cell value after each step, which reg_forward stores.
+    // quad ahead of each group of four steps (the blank's: one per half-chunk).  OWN: this wave
+    // holds column N (the others have no column-N code); hist: the cell value after each step,
+    // which reg_forward stores.
+    template <bool OWN, int P>
+    __device__ __forceinline__ static void reg_group(const RegOps& o, RegOps& n, const char* nb, int etq, int ebq,
+                                                     float& cur, unsigned& w, float (&hist)[OWN ? kChunk : 1]) {
+        n.et[P] = *reinterpret_cast<const float4*>(nb + P * kQS * 4 + etq);
+        if constexpr (P % 4 == 0) n.eb[P / 4] = *reinterpret_cast<const float4*>(nb + P * kQS * 4 + ebq);
+        __builtin_amdgcn_sched_barrier(0);
+        float nv[4];
+        reg_steps4<P == 0, P % 4>(cur, w, o.et[P], o.eb[P / 4], nv);
+        if constexpr (OWN) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) hist[4 * P + j] = nv[j];
+        }
+        cur = nv[3];
+        __builtin_amdgcn_sched_barrier(0);
+    }
     template <bool OWN>
     __device__ __forceinline__ static void reg_chunk(const RegOps& o, RegOps& n, const char* nb, int etq, int ebq,
                                                      float& cur, unsigned& w, float (&hist)[OWN ? kChunk : 1]) {
-#pragma unroll
-        for (int p = 0; p < kChunk / 4; ++p) {
-            n.et[p] = *reinterpret_cast<const float4*>(nb + p * kQS * 4 + etq);
-            n.eb[p] = *reinterpret_cast<const float4*>(nb + p * kQS * 4 + ebq);
-            __builtin_amdgcn_sched_barrier(0);
-            float nv[4];
-            if (p == 0)
-                reg_steps4<true>(cur, w, o.et[p], o.eb[p], nv);
-            else
-                reg_steps4<false>(cur, w, o.et[p], o.eb[p], nv);
-            if constexpr (OWN) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) hist[4 * p + j] = nv[j];
-            }
-            cur = nv[3];
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        static_assert(kChunk == 32, "eight groups of four steps");
+        reg_group<OWN, 0>(o, n, nb, etq, ebq, cur, w, hist);
+        reg_group<OWN, 1>(o, n, nb, etq, ebq, cur, w, hist);
+        reg_group<OWN, 2>(o, n, nb, etq, ebq, cur, w, hist);
+        reg_group<OWN, 3>(o, n, nb, etq, ebq, cur, w, hist);
+        reg_group<OWN, 4>(o, n, nb, etq, ebq, cur, w, hist);
+        reg_group<OWN, 5>(o, n, nb, etq, ebq, cur, w, hist);
+        reg_group<OWN, 6>(o, n, nb, etq, ebq, cur, w, hist);
+        reg_group<OWN, 7>(o, n, nb, etq, ebq, cur, w, hist);
     }
 
     // The DP waves' chunk loop of the register-resident split forward (run() sends them here;
