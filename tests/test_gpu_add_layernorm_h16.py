@@ -68,34 +68,49 @@ def test_without_b(dtype, D, rows):
     assert torch.equal(_bits(s), _bits(want_s))
 
 
-def test_validation():
-    """wx_add_layernorm's validation order, with the dtype checked beside D; legal pointers only."""
+@pytest.mark.parametrize("entry", ("wx_add_layernorm", "wx_add_layernorm_h16", "wx_add_layernorm_h16_dual"))
+def test_validation(entry):
+    """The validation the three entry points share, in wx_add_layernorm's order, each with its own rules:
+    wx_add_layernorm needs b (rows at a multiple of 4 floats) and y; the 16-bit ones check the dtype
+    beside D, take a null b (rows at a multiple of 8 elements) and need the 16-bit y; _dual's y32 may be
+    null.  Legal pointers only, and nothing is written by a refused call."""
     import ctypes
 
     from whisperx_amd import _lib
 
     lib = _lib.load()
+    half, dual = entry != "wx_add_layernorm", entry == "wx_add_layernorm_h16_dual"
+    outs = ("y32", "y16") if dual else ("y16",) if half else ("y32",)
     D, rows = 256, 4
     a = torch.zeros((rows, D), device="cuda")
-    b = torch.zeros((rows, D), dtype=torch.float16, device="cuda")
-    y = torch.full((rows, D), 7.0, dtype=torch.float16, device="cuda")
+    b = torch.zeros((rows, D), dtype=torch.float16 if half else torch.float32, device="cuda")
+    y32 = torch.full((rows, D), 7.0, device="cuda")
+    y16 = torch.full((rows, D), 7.0, dtype=torch.float16, device="cuda")
+    s = torch.full((rows, D), 7.0, device="cuda")
     g = torch.ones(D, device="cuda")
-    P = {"a": a.data_ptr(), "b": b.data_ptr(), "gamma": g.data_ptr(), "beta": g.data_ptr(), "y": y.data_ptr(), "sum": 0}
+    P = {"a": a.data_ptr(), "b": b.data_ptr(), "gamma": g.data_ptr(), "beta": g.data_ptr(), "y32": y32.data_ptr(),
+         "y16": y16.data_ptr(), "sum": 0}
 
     def call(rows=rows, D=D, sa=D, sb=D, dtype=1, **ptr):
         p = {k: ctypes.c_void_p(v) if v else None for k, v in {**P, **ptr}.items()}
-        return lib.wx_add_layernorm_h16(p["a"], p["b"], rows, D, sa, sb, p["gamma"], p["beta"], 1e-5, dtype, p["y"],
-                                        p["sum"], None)
+        return getattr(lib, entry)(p["a"], p["b"], rows, D, sa, sb, p["gamma"], p["beta"], 1e-5,
+                                   *((dtype,) if half else ()), *(p[o] for o in outs), p["sum"], None)
 
     INVALID = 1001
-    assert call(rows=-1) == INVALID and call(D=320) == INVALID and call(dtype=0) == INVALID and call(dtype=3) == INVALID
-    assert call(rows=0, a=0, y=0) == 0
-    for name in ("a", "gamma", "beta", "y"):
-        assert call(**{name: 0}) == INVALID
-    for name in ("a", "b", "gamma", "beta", "y"):
-        assert call(**{name: P[name] + 8}) == INVALID
-    assert call(sum=a.data_ptr() + 8) == INVALID
-    assert call(sa=D - 4) == INVALID and call(sa=D + 2) == INVALID and call(sb=D - 8) == INVALID and call(sb=D + 4) == INVALID
+    assert call(rows=-1) == INVALID and call(D=320) == INVALID
+    if half:
+        assert call(dtype=0) == INVALID and call(dtype=3) == INVALID and call(rows=0, dtype=0) == INVALID
+    assert call(rows=0, a=0, **{o: 0 for o in outs}) == 0
+    for name in ("a", "gamma", "beta") + (("y16",) if half else ("b", "y32")):
+        assert call(**{name: 0}) == INVALID, name
+    for name in ("a", "b", "gamma", "beta") + outs:
+        assert call(**{name: P[name] + 8}) == INVALID, name
+    assert call(sum=s.data_ptr() + 8) == INVALID
+    assert call(sa=D - 4) == INVALID and call(sa=D + 2) == INVALID
+    for sb in (D - 8, D + 4) if half else (D - 4, D + 2):  # too short; rows of b that are not 16-byte aligned
+        assert call(sb=sb) == INVALID, sb
     torch.cuda.synchronize()
-    assert bool((y == 7.0).all())
-    assert call() == 0 and call(b=0) == 0
+    assert bool((y32 == 7.0).all()) and bool((y16 == 7.0).all()) and bool((s == 7.0).all())
+    assert call() == 0 and call(sum=s.data_ptr()) == 0
+    for name in (("b",) if half else ()) + (("y32",) if dual else ()):  # the optional pointers
+        assert call(**{name: 0}) == 0, name

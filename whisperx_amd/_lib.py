@@ -23,6 +23,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("WX_LIB_PATH") or os.path.join(_HERE, "libwxalign.so")
 SRC_PATH = os.path.join(_HERE, "csrc", "wx_align.hip")
 SRC_PATHS = [SRC_PATH, os.path.join(_HERE, "csrc", "wx_binarize.hip"), os.path.join(_HERE, "csrc", "wx_emission.hip"),
+             os.path.join(_HERE, "csrc", "wx_add_layernorm.hip"),
              os.path.join(_HERE, "csrc", "wx_vad.hip"), os.path.join(_HERE, "csrc", "wx_diarize.hip"),
              os.path.join(_HERE, "csrc", "wx_mel.hip"), os.path.join(_HERE, "csrc", "wx_whisper.hip"),
              os.path.join(_HERE, "csrc", "wx_decode.hip"), os.path.join(_HERE, "csrc", "wx_beam.hip"),
@@ -908,26 +909,46 @@ def conv0_channel_norm(x: torch.Tensor, w: torch.Tensor, bias, stride: int, gamm
     return y
 
 
+def _add_layernorm(who: str, a: torch.Tensor, b: Optional[torch.Tensor], gamma: torch.Tensor, beta: torch.Tensor,
+                   eps: float, dtype: Optional[torch.dtype], dual: bool, want_y32: bool, want_sum: bool):
+    """add_layernorm (dtype None: b fp32) and add_layernorm_h16 / add_layernorm_h16_dual (b and y16 of `dtype`).
+    Returns (y32, y16, a + float(b)), None for what the call does not produce."""
+    lib = load()
+    half = dtype is not None
+    code = HALF_DTYPES.get(dtype)
+    if half and (code is None or a.dtype != torch.float32 or (b is not None and b.dtype != dtype)):
+        raise WXError(f"{who}: a must be float32 and b float16 / bfloat16 as `dtype` says, got {a.dtype}, "
+                      f"{None if b is None else b.dtype}, dtype {dtype}")
+    D = int(a.shape[-1])
+    if b is not None and tuple(a.shape) != tuple(b.shape):
+        raise WXError(f"{who}: shapes differ ({tuple(a.shape)}, {tuple(b.shape)})")
+
+    # the kernel reads 16-byte vectors: 16-byte aligned rows (row stride a multiple of 4 floats / 8 halves);
+    # an unaligned view is copied (contiguous) rather than refused
+    def rows_of(t, mult):
+        t = t.reshape(-1, D)
+        return t if t.data_ptr() % 16 == 0 and (t.shape[0] <= 1 or t.stride(0) % mult == 0) and t.stride(1) == 1 \
+            else t.contiguous()
+    a2, b2 = rows_of(a, 4), None if b is None else rows_of(b, 8 if half else 4)
+    rows = int(a2.shape[0])
+    y32 = torch.empty(a.shape, dtype=torch.float32, device=a.device) if want_y32 else None
+    y16 = torch.empty(a.shape, dtype=dtype, device=a.device) if half else None
+    s = torch.empty(a.shape, dtype=torch.float32, device=a.device) if want_sum else None
+    with torch.cuda.device(a.device):
+        _check(getattr(lib, "wx_" + who)(_ptr(a2), _ptr(b2), rows, D, int(a2.stride(0)) if rows else D,
+                                         int(b2.stride(0)) if rows and b2 is not None else D, _ptr(gamma), _ptr(beta),
+                                         float(eps), *((code,) if half else ()),
+                                         *((_ptr(y32), _ptr(y16)) if dual else (_ptr(y16 if half else y32),)), _ptr(s),
+                                         _stream(a.device)))
+    return y32, y16, s
+
+
 def add_layernorm(a: torch.Tensor, b: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float,
                   want_sum: bool = False):
     """wx_add_layernorm: LayerNorm(a + b) over the last dim of fp32 device tensors of one shape
     (last dim contiguous, rows at any stride the leading dims flatten to).  Returns y, or
     (y, a + b) with want_sum."""
-    lib = load()
-    D = int(a.shape[-1])
-    if tuple(a.shape) != tuple(b.shape):
-        raise WXError(f"add_layernorm: shapes differ ({tuple(a.shape)}, {tuple(b.shape)})")
-    # the kernel reads 16-byte vectors: 16-byte aligned rows (row stride a multiple of 4 floats);
-    # an unaligned view is copied (contiguous) rather than refused
-    a2, b2 = (t if t.data_ptr() % 16 == 0 and (t.shape[0] <= 1 or t.stride(0) % 4 == 0) and t.stride(1) == 1
-              else t.contiguous() for t in (a.reshape(-1, D), b.reshape(-1, D)))
-    rows = int(a2.shape[0])
-    y = torch.empty(a.shape, dtype=torch.float32, device=a.device)
-    s = torch.empty_like(y) if want_sum else None
-    with torch.cuda.device(a.device):
-        _check(lib.wx_add_layernorm(_ptr(a2), _ptr(b2), rows, D, int(a2.stride(0)) if rows else D,
-                                    int(b2.stride(0)) if rows else D, _ptr(gamma), _ptr(beta), float(eps), _ptr(y),
-                                    _ptr(s) if s is not None else None, _stream(a.device)))
+    y, _, s = _add_layernorm("add_layernorm", a, b, gamma, beta, eps, None, False, True, want_sum)
     return (y, s) if want_sum else y
 
 
@@ -978,27 +999,7 @@ def add_layernorm_h16(a: torch.Tensor, b: Optional[torch.Tensor], gamma: torch.T
     """wx_add_layernorm_h16: LayerNorm(a + float(b)) over the last dim, a fp32 and b of `dtype`
     (float16 / bfloat16) of one shape, or LayerNorm(a) with b None; the norm is computed in fp32
     and y is rounded to `dtype`.  Returns y, or (y, a + float(b)) with want_sum (the sum is fp32)."""
-    lib = load()
-    code = HALF_DTYPES.get(dtype)
-    if code is None or a.dtype != torch.float32 or (b is not None and b.dtype != dtype):
-        raise WXError(f"add_layernorm_h16: a must be float32 and b float16 / bfloat16 as `dtype` says, got {a.dtype}, "
-                      f"{None if b is None else b.dtype}, dtype {dtype}")
-    D = int(a.shape[-1])
-    if b is not None and tuple(a.shape) != tuple(b.shape):
-        raise WXError(f"add_layernorm_h16: shapes differ ({tuple(a.shape)}, {tuple(b.shape)})")
-
-    def rows_of(t, mult):  # 16-byte aligned rows, or a contiguous copy (as add_layernorm)
-        t = t.reshape(-1, D)
-        return t if t.data_ptr() % 16 == 0 and (t.shape[0] <= 1 or t.stride(0) % mult == 0) and t.stride(1) == 1 \
-            else t.contiguous()
-    a2, b2 = rows_of(a, 4), None if b is None else rows_of(b, 8)
-    rows = int(a2.shape[0])
-    y = torch.empty(a.shape, dtype=dtype, device=a.device)
-    s = torch.empty(a.shape, dtype=torch.float32, device=a.device) if want_sum else None
-    with torch.cuda.device(a.device):
-        _check(lib.wx_add_layernorm_h16(_ptr(a2), _ptr(b2), rows, D, int(a2.stride(0)) if rows else D,
-                                        int(b2.stride(0)) if rows and b2 is not None else D, _ptr(gamma), _ptr(beta),
-                                        float(eps), code, _ptr(y), _ptr(s), _stream(a.device)))
+    _, y, s = _add_layernorm("add_layernorm_h16", a, b, gamma, beta, eps, dtype, False, False, want_sum)
     return (y, s) if want_sum else y
 
 
@@ -1220,29 +1221,7 @@ def add_layernorm_h16_dual(a: torch.Tensor, b: Optional[torch.Tensor], gamma: to
     """wx_add_layernorm_h16_dual: LayerNorm(a + float(b)) (b None: LayerNorm(a)) over the last dim in
     one pass, a fp32 and b of `dtype`.  Returns (y32, y16): the norm in fp32 (None without want_y32)
     and its rounding to `dtype`; with want_sum (y32, y16, a + float(b))."""
-    lib = load()
-    code = HALF_DTYPES.get(dtype)
-    if code is None or a.dtype != torch.float32 or (b is not None and b.dtype != dtype):
-        raise WXError(f"add_layernorm_h16_dual: a must be float32 and b float16 / bfloat16 as `dtype` says, got "
-                      f"{a.dtype}, {None if b is None else b.dtype}, dtype {dtype}")
-    D = int(a.shape[-1])
-    if b is not None and tuple(a.shape) != tuple(b.shape):
-        raise WXError(f"add_layernorm_h16_dual: shapes differ ({tuple(a.shape)}, {tuple(b.shape)})")
-
-    def rows_of(t, mult):  # 16-byte aligned rows, or a contiguous copy (as add_layernorm)
-        t = t.reshape(-1, D)
-        return t if t.data_ptr() % 16 == 0 and (t.shape[0] <= 1 or t.stride(0) % mult == 0) and t.stride(1) == 1 \
-            else t.contiguous()
-    a2, b2 = rows_of(a, 4), None if b is None else rows_of(b, 8)
-    rows = int(a2.shape[0])
-    y32 = torch.empty(a.shape, dtype=torch.float32, device=a.device) if want_y32 else None
-    y16 = torch.empty(a.shape, dtype=dtype, device=a.device)
-    s = torch.empty(a.shape, dtype=torch.float32, device=a.device) if want_sum else None
-    with torch.cuda.device(a.device):
-        _check(lib.wx_add_layernorm_h16_dual(_ptr(a2), _ptr(b2), rows, D, int(a2.stride(0)) if rows else D,
-                                             int(b2.stride(0)) if rows and b2 is not None else D, _ptr(gamma),
-                                             _ptr(beta), float(eps), code, _ptr(y32), _ptr(y16), _ptr(s),
-                                             _stream(a.device)))
+    y32, y16, s = _add_layernorm("add_layernorm_h16_dual", a, b, gamma, beta, eps, dtype, True, want_y32, want_sum)
     return (y32, y16, s) if want_sum else (y32, y16)
 
 

@@ -1,7 +1,13 @@
 // wx_emission.hip — gfx950 kernels of the emission producer (reference
-// whisperx/alignment.py:226-233, the wav2vec2 forward): the first feature-encoder layer's
-// GroupNorm(512 groups = per channel over time) + GELU, fused, on time-major activations.
+// whisperx/alignment.py:226-233, the wav2vec2 forward) and their entry points: the channel norm
+// (wx_channel_norm), the first feature-encoder layer as conv + channel norm + GELU in one pass over
+// its output (wx_conv0_channel_norm, _h16), fp32 self-attention on the f32-input MFMA
+// (wx_attention_f32, _packed) and the positional convolution over packed segments
+// (wx_posconv_packed).  `layer_norm(residual + x)` is wx_add_layernorm.hip, the 16-bit attention
+// wx_attention_h16.hip.
 //
+// The channel norm: the first feature-encoder layer's GroupNorm(512 groups = per channel over time)
+// + GELU, fused, on time-major activations.
 // emission.prepare_model keeps the conv feature encoder time-major ([L, C], the GEMM route's
 // natural output).  torch's GroupNorm wants channel-major input, so on that layout it first
 // copied the 96k x 512 activation (196 MB for a 30 s segment) and then normalised it: ~1 ms per
@@ -22,6 +28,44 @@ constexpr int kCols = 64;    // channels per column tile (one wave-row of 64 lan
 constexpr int kRows = 4;     // waves per block, each striding rows
 constexpr int kSplit = 256;  // row slices per channel tile in pass 1
 
+// A block's kRows wave partials (s, q) of kCols columns, summed through LDS: wave 0 gets the sums
+// (.x, .y) of column `col`, the other waves what they gave.  In wave order, the own partial first;
+// PAIRWISE: (0 + 1) + (2 + 3).  Each caller keeps the order it was measured and pinned with.
+// (Arguments and result by value: partials passed by reference stay in memory until this is inlined,
+// and the loop that sums them is then compiled differently.)
+template <bool PAIRWISE = false>
+__device__ __forceinline__ double2 wave_partials(int wv, int col, double s, double q) {
+    __shared__ double ss[kRows][kCols], qq[kRows][kCols];
+    ss[wv][col] = s;
+    qq[wv][col] = q;
+    __syncthreads();
+    if (wv == 0) {
+        if constexpr (PAIRWISE) {
+            static_assert(kRows == 4, "two pairs");
+            s = (ss[0][col] + ss[1][col]) + (ss[2][col] + ss[3][col]);
+            q = (qq[0][col] + qq[1][col]) + (qq[2][col] + qq[3][col]);
+        } else {
+            for (int r = 1; r < kRows; ++r) {
+                s += ss[r][col];
+                q += qq[r][col];
+            }
+        }
+    }
+    return make_double2(s, q);
+}
+
+// A channel's (sum, sum of squares) over L values, folded with the affine: y = x * a + b with a = ab[c],
+// b = ab[C + c]
+__device__ __forceinline__ void chan_fold(double s, double q, int64_t L, int c, int C, const float* __restrict__ gamma,
+                                          const float* __restrict__ beta, float eps, float* __restrict__ ab) {
+    const double mean = s / (double)L;
+    const double var = fmax(q / (double)L - mean * mean, 0.0);  // biased, as GroupNorm
+    const double rstd = 1.0 / sqrt(var + (double)eps);
+    const double g = gamma ? (double)gamma[c] : 1.0, b = beta ? (double)beta[c] : 0.0;
+    ab[c] = (float)(rstd * g);
+    ab[C + c] = (float)(b - mean * rstd * g);
+}
+
 // pass 1: partial (sum, sum of squares) per (row slice, channel) in fp64
 __global__ __launch_bounds__(kCols * kRows) void chan_stats_kernel(const float* __restrict__ x, int64_t L, int C,
                                                                   double* __restrict__ part /* [kSplit][2][C] */) {
@@ -38,17 +82,10 @@ __global__ __launch_bounds__(kCols * kRows) void chan_stats_kernel(const float* 
             q += v * v;
         }
     }
-    __shared__ double ss[kRows][kCols], qq[kRows][kCols];
-    ss[r0][threadIdx.x & (kCols - 1)] = s;
-    qq[r0][threadIdx.x & (kCols - 1)] = q;
-    __syncthreads();
+    const double2 sq = wave_partials(r0, threadIdx.x & (kCols - 1), s, q);
     if (r0 == 0 && c < C) {
-        for (int r = 1; r < kRows; ++r) {
-            s += ss[r][threadIdx.x];
-            q += qq[r][threadIdx.x];
-        }
-        part[(int64_t)slice * 2 * C + c] = s;
-        part[(int64_t)slice * 2 * C + C + c] = q;
+        part[(int64_t)slice * 2 * C + c] = sq.x;
+        part[(int64_t)slice * 2 * C + C + c] = sq.y;
     }
 }
 
@@ -62,12 +99,7 @@ __global__ void chan_finish_kernel(const double* __restrict__ part, int64_t L, i
         s += part[(int64_t)k * 2 * C + c];
         q += part[(int64_t)k * 2 * C + C + c];
     }
-    const double mean = s / (double)L;
-    const double var = fmax(q / (double)L - mean * mean, 0.0);  // biased, as GroupNorm
-    const double rstd = 1.0 / sqrt(var + (double)eps);
-    const double g = gamma ? (double)gamma[c] : 1.0, b = beta ? (double)beta[c] : 0.0;
-    ab[c] = (float)(rstd * g);
-    ab[C + c] = (float)(b - mean * rstd * g);
+    chan_fold(s, q, L, c, C, gamma, beta, eps, ab);
 }
 
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
@@ -134,17 +166,10 @@ __global__ __launch_bounds__(256) void conv0_stats_kernel(const float* __restric
         s += v;
         q += v * v;
     }
-    __shared__ double ss[kRows][kCols], qq[kRows][kCols];
-    ss[wv][threadIdx.x & (kCols - 1)] = s;
-    qq[wv][threadIdx.x & (kCols - 1)] = q;
-    __syncthreads();
+    const double2 sq = wave_partials(wv, threadIdx.x & (kCols - 1), s, q);
     if (wv == 0 && c < C) {
-        for (int r = 1; r < kRows; ++r) {
-            s += ss[r][threadIdx.x];
-            q += qq[r][threadIdx.x];
-        }
-        part[(int64_t)blockIdx.y * 2 * C + c] = s;
-        part[(int64_t)blockIdx.y * 2 * C + C + c] = q;
+        part[(int64_t)blockIdx.y * 2 * C + c] = sq.x;
+        part[(int64_t)blockIdx.y * 2 * C + C + c] = sq.y;
     }
 }
 
@@ -177,48 +202,28 @@ __global__ __launch_bounds__(256) void conv0_finish_kernel(const double* __restr
             q += part[(int64_t)k * 2 * C + C + c];
         }
     }
-    __shared__ double ss[kRows][kCols], qq[kRows][kCols];
-    ss[g][threadIdx.x & (kCols - 1)] = s;
-    qq[g][threadIdx.x & (kCols - 1)] = q;
-    __syncthreads();
-    if (g != 0 || c >= C) return;
-    for (int r = 1; r < kRows; ++r) {
-        s += ss[r][threadIdx.x];
-        q += qq[r][threadIdx.x];
-    }
-    const double mean = s / (double)L;
-    const double var = fmax(q / (double)L - mean * mean, 0.0);  // biased, as GroupNorm
-    const double rstd = 1.0 / sqrt(var + (double)eps);
-    const double gg = gamma ? (double)gamma[c] : 1.0, bb = beta ? (double)beta[c] : 0.0;
-    ab[c] = (float)(rstd * gg);
-    ab[C + c] = (float)(bb - mean * rstd * gg);
+    const double2 sq = wave_partials(g, threadIdx.x & (kCols - 1), s, q);
+    if (g == 0 && c < C) chan_fold(sq.x, sq.y, L, c, C, gamma, beta, eps, ab);
 }
 
-__device__ __forceinline__ float gelu_erf0(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
-
-// The apply passes' store (OT: 0 fp32, else the WX_DTYPE_* code of wx_conv0_channel_norm_h16): the
-// fp32 value, computed by the same expressions whatever OT is, rounded to nearest even on the way out.
-template <int OT>
+// The apply passes' store (ET: wx::kF32, or the dtype of wx_conv0_channel_norm_h16): the fp32 value,
+// computed by the same expressions whatever ET is, rounded to nearest even on the way out.
+template <int ET>
 struct C0Out {
+    using type = short;
+    static __device__ __forceinline__ short put(float v) { return wx::round16<ET>(v); }
+};
+template <>
+struct C0Out<wx::kF32> {
     using type = float;
     static __device__ __forceinline__ float put(float v) { return v; }
 };
-template <>
-struct C0Out<WX_DTYPE_F16> {
-    using type = unsigned short;
-    static __device__ __forceinline__ unsigned short put(float v) { return __builtin_bit_cast(unsigned short, (_Float16)v); }
-};
-template <>
-struct C0Out<WX_DTYPE_BF16> {
-    using type = unsigned short;
-    static __device__ __forceinline__ unsigned short put(float v) { return __builtin_bit_cast(unsigned short, (__bf16)v); }
-};
 
-template <int K, int OT = 0>
+template <int K, int ET = wx::kF32>
 __global__ __launch_bounds__(256) void conv0_apply_kernel(const float* __restrict__ x, int64_t L, int stride,
                                                           const float* __restrict__ wt, int C,
                                                           const float* __restrict__ ab, int gelu,
-                                                          typename C0Out<OT>::type* __restrict__ y) {
+                                                          typename C0Out<ET>::type* __restrict__ y) {
     const int c = blockIdx.x * kCols + (threadIdx.x & (kCols - 1));
     const int wv = threadIdx.x / kCols;
     if (c >= C) return;
@@ -232,8 +237,8 @@ __global__ __launch_bounds__(256) void conv0_apply_kernel(const float* __restric
         const int64_t t = t0 + r;
         if (t >= L) break;
         float v = conv0_at<K>(x, t, stride, w) * sa + sb;
-        if (gelu) v = gelu_erf0(v);
-        y[t * C + c] = C0Out<OT>::put(v);
+        if (gelu) v = gelu_erf(v);
+        y[t * C + c] = C0Out<ET>::put(v);
     }
 }
 
@@ -282,6 +287,28 @@ __device__ __forceinline__ float conv0_row_s(const float* __restrict__ xs /* wav
     return acc;
 }
 
+// The register-resident passes' walk over a wave's rows, the channel's taps in w:
+// acc = f(acc, r, v) for r = 0 .. kC0R - 1, v the convolution at row t0 + r, on whichever of the two
+// forms the wave's samples allow.  Rows at or past L are walked too (their samples read as zeros): f
+// tests r.  What a pass carries from row to row goes through acc by value (the apply pass: nothing):
+// sums that f updated through references were compiled to a branch per row, with the sample loads
+// split between them, instead of the selects and the ten 16-dword loads of the loops written out.
+template <int K, int S, class A, class F>
+__device__ __forceinline__ A conv0_rows_rl(const float* __restrict__ x, int64_t nsamp, int64_t t0,
+                                           const float (&w)[K], A acc, F f) {
+    if (t0 * S + (kC0R - 1) * S + K <= nsamp) {
+        const float* xs = x + t0 * S;
+#pragma unroll
+        for (int r = 0; r < kC0R; ++r) acc = f(acc, r, conv0_row_s<K, S>(xs, r, w));
+    } else {
+        float sv[((kC0R - 1) * S + K + 63) / 64];
+        conv0_samples<K, S>(x, nsamp, t0, sv);
+#pragma unroll
+        for (int r = 0; r < kC0R; ++r) acc = f(acc, r, conv0_row<K, S>(sv, r, w));
+    }
+    return acc;
+}
+
 template <int K, int S>
 __global__ __launch_bounds__(256) void conv0_stats_rl_kernel(const float* __restrict__ x, int64_t nsamp, int64_t L,
                                                              const float* __restrict__ wt, int C,
@@ -292,48 +319,29 @@ __global__ __launch_bounds__(256) void conv0_stats_rl_kernel(const float* __rest
     float w[K];
 #pragma unroll
     for (int j = 0; j < K; ++j) w[j] = wt[(int64_t)cc * K + j];
-    const int64_t t0 = ((int64_t)blockIdx.y * 4 + wv) * kC0R;
+    const int64_t t0 = ((int64_t)blockIdx.y * kRows + wv) * kC0R;
     const int64_t nr = L - t0;
-    double sm = 0.0, q = 0.0;
-    if (t0 * S + (kC0R - 1) * S + K <= nsamp) {
-        const float* xs = x + t0 * S;
-#pragma unroll
-        for (int r = 0; r < kC0R; ++r) {
-            const double d = (double)conv0_row_s<K, S>(xs, r, w);
-            if (r < nr) {
-                sm += d;
-                q = fma(d, d, q);
-            }
+    const auto add = [=](double2 a, int r, float v) {  // a: (sum, sum of squares)
+        const double d = (double)v;
+        if (r < nr) {
+            a.x += d;
+            a.y = fma(d, d, a.y);
         }
-    } else {
-        float sv[((kC0R - 1) * S + K + 63) / 64];
-        conv0_samples<K, S>(x, nsamp, t0, sv);
-#pragma unroll
-        for (int r = 0; r < kC0R; ++r) {
-            const double d = (double)conv0_row<K, S>(sv, r, w);
-            if (r < nr) {
-                sm += d;
-                q = fma(d, d, q);
-            }
-        }
-    }
-    __shared__ double ss[4][64], qq[4][64];
-    ss[wv][lc] = sm;
-    qq[wv][lc] = q;
-    __syncthreads();
+        return a;
+    };
+    const double2 own = conv0_rows_rl<K, S>(x, nsamp, t0, w, make_double2(0.0, 0.0), add);
+    const double2 sq = wave_partials<true>(wv, lc, own.x, own.y);
     if (wv == 0 && c < C) {
-        sm = (ss[0][lc] + ss[1][lc]) + (ss[2][lc] + ss[3][lc]);
-        q = (qq[0][lc] + qq[1][lc]) + (qq[2][lc] + qq[3][lc]);
-        part[(int64_t)blockIdx.y * 2 * C + c] = sm;
-        part[(int64_t)blockIdx.y * 2 * C + C + c] = q;
+        part[(int64_t)blockIdx.y * 2 * C + c] = sq.x;
+        part[(int64_t)blockIdx.y * 2 * C + C + c] = sq.y;
     }
 }
 
-template <int K, int S, int OT = 0>
+template <int K, int S, int ET = wx::kF32>
 __global__ __launch_bounds__(256) void conv0_apply_rl_kernel(const float* __restrict__ x, int64_t nsamp, int64_t L,
                                                              const float* __restrict__ wt, int C,
                                                              const float* __restrict__ ab, int gelu,
-                                                             typename C0Out<OT>::type* __restrict__ y) {
+                                                             typename C0Out<ET>::type* __restrict__ y) {
     const int lc = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int c = blockIdx.x * 64 + lc;
     const int cc = min(c, C - 1);
@@ -341,27 +349,15 @@ __global__ __launch_bounds__(256) void conv0_apply_rl_kernel(const float* __rest
 #pragma unroll
     for (int j = 0; j < K; ++j) w[j] = wt[(int64_t)cc * K + j];
     const float sa = ab[cc], sb = ab[C + cc];
-    const int64_t t0 = ((int64_t)blockIdx.y * 4 + wv) * kC0R;
+    const int64_t t0 = ((int64_t)blockIdx.y * kRows + wv) * kC0R;
     const int64_t nr = L - t0;
-    typename C0Out<OT>::type* yr = y + t0 * C + c;  // (row r at yr + r C)
-    if (t0 * S + (kC0R - 1) * S + K <= nsamp) {
-        const float* xs = x + t0 * S;
-#pragma unroll
-        for (int r = 0; r < kC0R; ++r) {
-            float v = conv0_row_s<K, S>(xs, r, w) * sa + sb;
-            if (gelu) v = gelu_erf0(v);
-            if (r < nr && c < C) yr[(int64_t)r * C] = C0Out<OT>::put(v);
-        }
-    } else {
-        float sv[((kC0R - 1) * S + K + 63) / 64];
-        conv0_samples<K, S>(x, nsamp, t0, sv);
-#pragma unroll
-        for (int r = 0; r < kC0R; ++r) {
-            float v = conv0_row<K, S>(sv, r, w) * sa + sb;
-            if (gelu) v = gelu_erf0(v);
-            if (r < nr && c < C) yr[(int64_t)r * C] = C0Out<OT>::put(v);
-        }
-    }
+    typename C0Out<ET>::type* yr = y + t0 * C + c;  // (row r at yr + r C)
+    conv0_rows_rl<K, S>(x, nsamp, t0, w, 0, [=](int, int r, float v) {
+        v = v * sa + sb;
+        if (gelu) v = gelu_erf(v);
+        if (r < nr && c < C) yr[(int64_t)r * C] = C0Out<ET>::put(v);
+        return 0;
+    });
 }
 
 // ------------------------------------------------------------------------------------
@@ -605,194 +601,6 @@ __global__ __launch_bounds__(64 * SPLIT) __attribute__((amdgpu_waves_per_eu(2)))
     }
 }
 
-// Residual add + LayerNorm over rows of D floats (the wav2vec2 encoder layer's
-// `layer_norm(residual + x)`, twice per layer): one wave per row, the row in registers (D / 256
-// float4 per lane), mean and biased variance in fp32 from the registers (two passes, not
-// torch's Welford: equal to fp32 tolerance), y = (s - mean) * rstd * gamma + beta.  Optionally
-// also writes the sum s (the pre-norm residual stream of the stable-layer-norm layers).
-// D4 < 64 NV (Whisper-tiny's D = 384: 96 float4): the lanes past the row's end hold zeros and
-// skip their loads and stores; the full-width instantiations compile as before.
-template <int NV, int D4 = 64 * NV>  // NV float4 per lane, D4 per row: D = 4 D4
-__global__ __launch_bounds__(256) void add_ln_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                      float eps, int64_t rows, int64_t sa, int64_t sb, int64_t sy,
-                                                      float* __restrict__ y, float* __restrict__ sum_out) {
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int l = threadIdx.x & 63;
-    constexpr int D = 4 * D4;
-    constexpr bool kFull = D4 == 64 * NV;
-    static_assert(D4 <= 64 * NV && D4 > 64 * (NV - 1), "NV float4 per lane cover the row");
-    const float4* pa = reinterpret_cast<const float4*>(a + row * sa);
-    const float4* pb = reinterpret_cast<const float4*>(b + row * sb);
-    float4 v[NV];
-    float acc = 0.0f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        if (!kFull && 64 * i + l >= D4) {
-            v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            continue;
-        }
-        const float4 x = pa[64 * i + l], z = pb[64 * i + l];
-        v[i] = make_float4(x.x + z.x, x.y + z.y, x.z + z.z, x.w + z.w);
-        acc += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    const float mean = acc / (float)D;
-    float q = 0.0f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        if (!kFull && 64 * i + l >= D4) continue;
-        const float dx = v[i].x - mean, dy = v[i].y - mean, dz = v[i].z - mean, dw = v[i].w - mean;
-        q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
-    const float rstd = 1.0f / sqrtf(q / (float)D + eps);
-    float4* py = reinterpret_cast<float4*>(y + row * sy);
-    float4* ps = sum_out ? reinterpret_cast<float4*>(sum_out + row * sy) : nullptr;
-    const float4* pg = reinterpret_cast<const float4*>(gamma);
-    const float4* pt = reinterpret_cast<const float4*>(beta);
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        if (!kFull && 64 * i + l >= D4) continue;
-        const float4 g = pg[64 * i + l], t = pt[64 * i + l];
-        py[64 * i + l] = make_float4((v[i].x - mean) * rstd * g.x + t.x, (v[i].y - mean) * rstd * g.y + t.y,
-                                     (v[i].z - mean) * rstd * g.z + t.z, (v[i].w - mean) * rstd * g.w + t.w);
-        if (ps) ps[64 * i + l] = v[i];
-    }
-}
-
-// add_ln_kernel between WhisperEncoder's fp32 residual stream and its 16-bit GEMMs
-// (wx_add_layernorm_h16): b holds fp16 / bf16 elements (BF) and is widened on the load (a null b:
-// zeros, added like any other, so that the result is add_ln_kernel's on a zero b), y is rounded
-// to nearest even on the store, the sum stays fp32.  Everything between is add_ln_kernel's,
-// expression for expression: y is bit for bit the rounding of its y.
-template <bool BF, int NV, int D4 = 64 * NV>
-__global__ __launch_bounds__(256) void add_ln_h16_kernel(const float* __restrict__ a, const unsigned short* __restrict__ b,
-                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                          float eps, int64_t rows, int64_t sa, int64_t sb, int64_t sy,
-                                                          unsigned short* __restrict__ y, float* __restrict__ sum_out) {
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int l = threadIdx.x & 63;
-    constexpr int D = 4 * D4, ET = wx::half_et(BF);
-    constexpr bool kFull = D4 == 64 * NV;
-    static_assert(D4 <= 64 * NV && D4 > 64 * (NV - 1), "NV float4 per lane cover the row");
-    const float4* pa = reinterpret_cast<const float4*>(a + row * sa);
-    const ushort4* pb = b ? reinterpret_cast<const ushort4*>(b + row * sb) : nullptr;
-    float4 v[NV];
-    float acc = 0.0f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        if (!kFull && 64 * i + l >= D4) {
-            v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            continue;
-        }
-        const float4 x = pa[64 * i + l];
-        float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (pb) {
-            const ushort4 u = pb[64 * i + l];
-            z = make_float4(wx::widen16<ET>(u.x), wx::widen16<ET>(u.y), wx::widen16<ET>(u.z), wx::widen16<ET>(u.w));
-        }
-        v[i] = make_float4(x.x + z.x, x.y + z.y, x.z + z.z, x.w + z.w);
-        acc += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    const float mean = acc / (float)D;
-    float q = 0.0f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        if (!kFull && 64 * i + l >= D4) continue;
-        const float dx = v[i].x - mean, dy = v[i].y - mean, dz = v[i].z - mean, dw = v[i].w - mean;
-        q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
-    const float rstd = 1.0f / sqrtf(q / (float)D + eps);
-    ushort4* py = reinterpret_cast<ushort4*>(y + row * sy);
-    float4* ps = sum_out ? reinterpret_cast<float4*>(sum_out + row * sy) : nullptr;
-    const float4* pg = reinterpret_cast<const float4*>(gamma);
-    const float4* pt = reinterpret_cast<const float4*>(beta);
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        if (!kFull && 64 * i + l >= D4) continue;
-        const float4 g = pg[64 * i + l], t = pt[64 * i + l];
-        py[64 * i + l] = make_ushort4(wx::round16<ET>((v[i].x - mean) * rstd * g.x + t.x),
-                                      wx::round16<ET>((v[i].y - mean) * rstd * g.y + t.y),
-                                      wx::round16<ET>((v[i].z - mean) * rstd * g.z + t.z),
-                                      wx::round16<ET>((v[i].w - mean) * rstd * g.w + t.w));
-        if (ps) ps[64 * i + l] = v[i];
-    }
-}
-
-// add_ln_h16_kernel with both forms of the norm's output (wx_add_layernorm_h16_dual): a post-norm
-// wav2vec2 layer needs norm(residual + x) in fp32 as the next residual and in 16 bit as the next GEMM
-// operand.  One pass over the row: y32 (optional) is add_ln_kernel's y on float(b) bit for bit, y16
-// its rounding to nearest even (add_ln_h16_kernel's y); the expressions are theirs.
-template <bool BF, int NV, int D4 = 64 * NV>
-__global__ __launch_bounds__(256) void add_ln_dual_kernel(const float* __restrict__ a, const unsigned short* __restrict__ b,
-                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                           float eps, int64_t rows, int64_t sa, int64_t sb, int64_t sy,
-                                                           float* __restrict__ y32, unsigned short* __restrict__ y16,
-                                                           float* __restrict__ sum_out) {
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int l = threadIdx.x & 63;
-    constexpr int D = 4 * D4, ET = wx::half_et(BF);
-    constexpr bool kFull = D4 == 64 * NV;
-    static_assert(D4 <= 64 * NV && D4 > 64 * (NV - 1), "NV float4 per lane cover the row");
-    const float4* pa = reinterpret_cast<const float4*>(a + row * sa);
-    const ushort4* pb = b ? reinterpret_cast<const ushort4*>(b + row * sb) : nullptr;
-    float4 v[NV];
-    float acc = 0.0f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        if (!kFull && 64 * i + l >= D4) {
-            v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            continue;
-        }
-        const float4 x = pa[64 * i + l];
-        float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (pb) {
-            const ushort4 u = pb[64 * i + l];
-            z = make_float4(wx::widen16<ET>(u.x), wx::widen16<ET>(u.y), wx::widen16<ET>(u.z), wx::widen16<ET>(u.w));
-        }
-        v[i] = make_float4(x.x + z.x, x.y + z.y, x.z + z.z, x.w + z.w);
-        acc += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    const float mean = acc / (float)D;
-    float q = 0.0f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        if (!kFull && 64 * i + l >= D4) continue;
-        const float dx = v[i].x - mean, dy = v[i].y - mean, dz = v[i].z - mean, dw = v[i].w - mean;
-        q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
-    const float rstd = 1.0f / sqrtf(q / (float)D + eps);
-    float4* p32 = y32 ? reinterpret_cast<float4*>(y32 + row * sy) : nullptr;
-    ushort4* p16 = reinterpret_cast<ushort4*>(y16 + row * sy);
-    float4* ps = sum_out ? reinterpret_cast<float4*>(sum_out + row * sy) : nullptr;
-    const float4* pg = reinterpret_cast<const float4*>(gamma);
-    const float4* pt = reinterpret_cast<const float4*>(beta);
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        if (!kFull && 64 * i + l >= D4) continue;
-        const float4 g = pg[64 * i + l], t = pt[64 * i + l];
-        const float4 y = make_float4((v[i].x - mean) * rstd * g.x + t.x, (v[i].y - mean) * rstd * g.y + t.y,
-                                     (v[i].z - mean) * rstd * g.z + t.z, (v[i].w - mean) * rstd * g.w + t.w);
-        if (p32) p32[64 * i + l] = y;
-        p16[64 * i + l] = make_ushort4(wx::round16<ET>(y.x), wx::round16<ET>(y.y), wx::round16<ET>(y.z), wx::round16<ET>(y.w));
-        if (ps) ps[64 * i + l] = v[i];
-    }
-}
-
 // ------------------------------------------------------------------------------------
 // wav2vec2 positional convolution over packed segments (alignment.py:226-233: the encoder's
 // Wav2Vec2PositionalConvEmbedding — Conv1d(D, D, K = 128, padding K / 2, groups G), the last
@@ -938,7 +746,7 @@ __global__ __launch_bounds__(256) void posconv_kernel(PosConvArgs a) {
             for (int ob = 0; ob < NOB; ++ob) {
                 const int c = 16 * ob + r16;
                 float y = acc[fb][ob][v] + (a.bias ? a.bias[g * CG + c] : 0.f);
-                y = gelu_erf0(y);
+                y = gelu_erf(y);
                 if (a.residual) y += a.h[rb + c];
                 a.out[rb + c] = y;
             }
@@ -978,14 +786,14 @@ extern "C" size_t wx_conv0_channel_norm_workspace_bytes(int64_t L, int32_t C) {
 
 namespace wxe {
 
-// wx_conv0_channel_norm (OT 0, y fp32) and wx_conv0_channel_norm_h16 (OT a WX_DTYPE_* code, y 16 bit):
+// wx_conv0_channel_norm (ET wx::kF32, y fp32) and wx_conv0_channel_norm_h16 (ET its dtype, y 16 bit):
 // the same statistics passes, the apply pass instantiated for the output type
-template <int OT>
+template <int ET>
 static int conv0_channel_norm(const float* x, int64_t S, int32_t K, int32_t stride, const float* w, int32_t C,
                               const float* gamma, const float* beta, float eps, int32_t gelu, void* yv, void* workspace,
                               size_t workspace_bytes, void* stream) {
     if (S < 0 || C <= 0 || K < 1 || K > kC0MaxK || stride < 1 || !x || !w || !yv) return WX_E_INVALID;
-    typename C0Out<OT>::type* y = static_cast<typename C0Out<OT>::type*>(yv);
+    typename C0Out<ET>::type* y = static_cast<typename C0Out<ET>::type*>(yv);
     const int64_t L = S >= K ? (S - K) / stride + 1 : 0;
     if (L == 0) return WX_OK;
     if (!workspace || workspace_bytes < wx_conv0_channel_norm_workspace_bytes(L, C)) return WX_E_WORKSPACE;
@@ -1001,7 +809,7 @@ static int conv0_channel_norm(const float* x, int64_t S, int32_t K, int32_t stri
         hipLaunchKernelGGL((conv0_stats_rl_kernel<10, 5>), grid, dim3(256), 0, st, x, S, L, w, C, part);
         hipLaunchKernelGGL(conv0_finish_kernel, dim3((C + kCols - 1) / kCols), dim3(kCols * kRows), 0, st, part,
                            (int)nblk, L, C, gamma, beta, eps, ab);
-        hipLaunchKernelGGL((conv0_apply_rl_kernel<10, 5, OT>), grid, dim3(256), 0, st, x, S, L, w, C, ab, gelu, y);
+        hipLaunchKernelGGL((conv0_apply_rl_kernel<10, 5, ET>), grid, dim3(256), 0, st, x, S, L, w, C, ab, gelu, y);
         return wx::launch_status();
     }
     const dim3 grid((C + kCols - 1) / kCols, (unsigned)nblk), blk(kCols * kRows);
@@ -1010,7 +818,7 @@ static int conv0_channel_norm(const float* x, int64_t S, int32_t K, int32_t stri
         hipLaunchKernelGGL(conv0_stats_kernel<KK>, grid, blk, 0, st, x, L, stride, w, C, part);           \
         hipLaunchKernelGGL(conv0_finish_kernel, dim3((C + kCols - 1) / kCols), blk, 0, st, part, (int)nblk, L, C, \
                            gamma, beta, eps, ab);                                                              \
-        hipLaunchKernelGGL((conv0_apply_kernel<KK, OT>), grid, blk, 0, st, x, L, stride, w, C, ab, gelu, y); \
+        hipLaunchKernelGGL((conv0_apply_kernel<KK, ET>), grid, blk, 0, st, x, L, stride, w, C, ab, gelu, y); \
         break;
     switch (K) {
         WX_C0(1) WX_C0(2) WX_C0(3) WX_C0(4) WX_C0(5) WX_C0(6) WX_C0(7) WX_C0(8) WX_C0(9) WX_C0(10) WX_C0(11)
@@ -1027,7 +835,7 @@ extern "C" int wx_conv0_channel_norm(const float* x, int64_t S, int32_t K, int32
                                      const float* bias, int32_t C, const float* gamma, const float* beta, float eps,
                                      int32_t gelu, float* y, void* workspace, size_t workspace_bytes, void* stream) {
     (void)bias;  // cancels in the per-channel normalisation (see above): never added
-    return wxe::conv0_channel_norm<0>(x, S, K, stride, w, C, gamma, beta, eps, gelu, y, workspace, workspace_bytes,
+    return wxe::conv0_channel_norm<wx::kF32>(x, S, K, stride, w, C, gamma, beta, eps, gelu, y, workspace, workspace_bytes,
                                       stream);
 }
 
@@ -1037,10 +845,10 @@ extern "C" int wx_conv0_channel_norm_h16(const float* x, int64_t S, int32_t K, i
                                          void* stream) {
     (void)bias;
     if (dtype == WX_DTYPE_F16)
-        return wxe::conv0_channel_norm<WX_DTYPE_F16>(x, S, K, stride, w, C, gamma, beta, eps, gelu, y, workspace,
+        return wxe::conv0_channel_norm<wx::kF16>(x, S, K, stride, w, C, gamma, beta, eps, gelu, y, workspace,
                                                      workspace_bytes, stream);
     if (dtype == WX_DTYPE_BF16)
-        return wxe::conv0_channel_norm<WX_DTYPE_BF16>(x, S, K, stride, w, C, gamma, beta, eps, gelu, y, workspace,
+        return wxe::conv0_channel_norm<wx::kBF16>(x, S, K, stride, w, C, gamma, beta, eps, gelu, y, workspace,
                                                       workspace_bytes, stream);
     return WX_E_INVALID;
 }
@@ -1132,108 +940,6 @@ extern "C" int wx_attention_f32_packed(const float* q, const float* k, const flo
         case 4: hipLaunchKernelGGL((attn_f32_kernel<4, true>), dim3((unsigned)n_units), dim3(256), 0, s, a); break;
         default: return WX_E_INVALID;
     }
-    return wx::launch_status();
-}
-
-extern "C" int wx_add_layernorm(const float* a, const float* b, int64_t rows, int32_t D, int64_t a_stride,
-                                int64_t b_stride, const float* gamma, const float* beta, float eps, float* y,
-                                float* sum_out, void* stream) {
-    using namespace wxe;
-    if (rows < 0 || (D != 768 && D != 1024 && D != 512 && D != 256 && D != 384 && D != 1280)) return WX_E_INVALID;
-    if (rows == 0) return WX_OK;  // (an empty tensor may have no storage)
-    if (!a || !b || !gamma || !beta || !y) return WX_E_INVALID;
-    if (a_stride < D || b_stride < D || (a_stride & 3) || (b_stride & 3)) return WX_E_INVALID;
-    for (const void* p : {(const void*)a, (const void*)b, (const void*)gamma, (const void*)beta, (const void*)y})
-        if (reinterpret_cast<uintptr_t>(p) & 15) return WX_E_INVALID;
-    if (sum_out && (reinterpret_cast<uintptr_t>(sum_out) & 15)) return WX_E_INVALID;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)((rows + 3) / 4));
-    switch (D) {
-        case 256: hipLaunchKernelGGL(add_ln_kernel<1>, grid, dim3(256), 0, st, a, b, gamma, beta, eps, rows, a_stride, b_stride, (int64_t)D, y, sum_out); break;
-        case 512: hipLaunchKernelGGL(add_ln_kernel<2>, grid, dim3(256), 0, st, a, b, gamma, beta, eps, rows, a_stride, b_stride, (int64_t)D, y, sum_out); break;
-        case 768: hipLaunchKernelGGL(add_ln_kernel<3>, grid, dim3(256), 0, st, a, b, gamma, beta, eps, rows, a_stride, b_stride, (int64_t)D, y, sum_out); break;
-        case 384: hipLaunchKernelGGL((add_ln_kernel<2, 96>), grid, dim3(256), 0, st, a, b, gamma, beta, eps, rows, a_stride, b_stride, (int64_t)D, y, sum_out); break;
-        case 1280: hipLaunchKernelGGL(add_ln_kernel<5>, grid, dim3(256), 0, st, a, b, gamma, beta, eps, rows, a_stride, b_stride, (int64_t)D, y, sum_out); break;
-        default: hipLaunchKernelGGL(add_ln_kernel<4>, grid, dim3(256), 0, st, a, b, gamma, beta, eps, rows, a_stride, b_stride, (int64_t)D, y, sum_out); break;
-    }
-    return wx::launch_status();
-}
-
-extern "C" int wx_add_layernorm_h16(const float* a, const void* b, int64_t rows, int32_t D, int64_t a_stride,
-                                    int64_t b_stride, const float* gamma, const float* beta, float eps, int32_t dtype,
-                                    void* y, float* sum_out, void* stream) {
-    using namespace wxe;
-    if (rows < 0 || (D != 768 && D != 1024 && D != 512 && D != 256 && D != 384 && D != 1280) ||
-        (dtype != WX_DTYPE_F16 && dtype != WX_DTYPE_BF16))
-        return WX_E_INVALID;
-    if (rows == 0) return WX_OK;  // (an empty tensor may have no storage)
-    if (!a || !gamma || !beta || !y) return WX_E_INVALID;
-    if (a_stride < D || (a_stride & 3) || (b && (b_stride < D || (b_stride & 7)))) return WX_E_INVALID;
-    for (const void* p : {(const void*)a, b, (const void*)gamma, (const void*)beta, (const void*)y})
-        if (reinterpret_cast<uintptr_t>(p) & 15) return WX_E_INVALID;
-    if (sum_out && (reinterpret_cast<uintptr_t>(sum_out) & 15)) return WX_E_INVALID;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)((rows + 3) / 4));
-    const unsigned short* bh = static_cast<const unsigned short*>(b);
-    unsigned short* yh = static_cast<unsigned short*>(y);
-#define WX_LN16(BF, ...)                                                                                        \
-    hipLaunchKernelGGL((add_ln_h16_kernel<BF, __VA_ARGS__>), grid, dim3(256), 0, st, a, bh, gamma, beta, eps, rows, \
-                       a_stride, b_stride, (int64_t)D, yh, sum_out)
-#define WX_LN16_D(BF)                             \
-    switch (D) {                                  \
-        case 256: WX_LN16(BF, 1); break;          \
-        case 512: WX_LN16(BF, 2); break;          \
-        case 768: WX_LN16(BF, 3); break;          \
-        case 384: WX_LN16(BF, 2, 96); break;      \
-        case 1280: WX_LN16(BF, 5); break;         \
-        default: WX_LN16(BF, 4); break;           \
-    }
-    if (dtype == WX_DTYPE_BF16) {
-        WX_LN16_D(true)
-    } else {
-        WX_LN16_D(false)
-    }
-#undef WX_LN16_D
-#undef WX_LN16
-    return wx::launch_status();
-}
-
-extern "C" int wx_add_layernorm_h16_dual(const float* a, const void* b, int64_t rows, int32_t D, int64_t a_stride,
-                                         int64_t b_stride, const float* gamma, const float* beta, float eps,
-                                         int32_t dtype, float* y32, void* y16, float* sum_out, void* stream) {
-    using namespace wxe;
-    if (rows < 0 || (D != 768 && D != 1024 && D != 512 && D != 256 && D != 384 && D != 1280) ||
-        (dtype != WX_DTYPE_F16 && dtype != WX_DTYPE_BF16))
-        return WX_E_INVALID;
-    if (rows == 0) return WX_OK;  // (an empty tensor may have no storage)
-    if (!a || !gamma || !beta || !y16) return WX_E_INVALID;
-    if (a_stride < D || (a_stride & 3) || (b && (b_stride < D || (b_stride & 7)))) return WX_E_INVALID;
-    for (const void* p : {(const void*)a, b, (const void*)gamma, (const void*)beta, (const void*)y32, (const void*)y16,
-                          (const void*)sum_out})
-        if (reinterpret_cast<uintptr_t>(p) & 15) return WX_E_INVALID;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)((rows + 3) / 4));
-    const unsigned short* bh = static_cast<const unsigned short*>(b);
-    unsigned short* yh = static_cast<unsigned short*>(y16);
-#define WX_LND(BF, ...)                                                                                          \
-    hipLaunchKernelGGL((add_ln_dual_kernel<BF, __VA_ARGS__>), grid, dim3(256), 0, st, a, bh, gamma, beta, eps, rows, \
-                       a_stride, b_stride, (int64_t)D, y32, yh, sum_out)
-#define WX_LND_D(BF)                             \
-    switch (D) {                                 \
-        case 256: WX_LND(BF, 1); break;          \
-        case 512: WX_LND(BF, 2); break;          \
-        case 768: WX_LND(BF, 3); break;          \
-        case 384: WX_LND(BF, 2, 96); break;      \
-        case 1280: WX_LND(BF, 5); break;         \
-        default: WX_LND(BF, 4); break;           \
-    }
-    if (dtype == WX_DTYPE_BF16) {
-        WX_LND_D(true)
-    } else {
-        WX_LND_D(false)
-    }
-#undef WX_LND_D
-#undef WX_LND
     return wx::launch_status();
 }
 
