@@ -609,6 +609,42 @@ int wx_decode_attention_h16_grouped(const void* q, const void* k, const void* v,
                                     const int64_t* k_strides, const int64_t* v_strides, float scale, int32_t dtype,
                                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* The self-attention of one decode step at a position held in DEVICE memory, with the cache append
+ * fused (WhisperDecoder.start(graph=True): the launch is the same at every step, so a captured
+ * graph can replay it).  With p = *pos, read by the kernels when they run:
+ *   - row p of k_cache / v_cache of every (b, h) becomes the (b, h) row of k_new / v_new, bit for bit;
+ *   - o[b][h][:] is the attention of q[b][h][:] over the rows 0 .. p, row p taken from k_new / v_new:
+ *     bit-identical to wx_decode_attention_f32 (_h16) with L = p + 1 on the cache after that copy;
+ *   - rows above p are neither read nor written;
+ *   - p < 0 or p >= Lcap: nothing at all is written (defined behaviour, not an error).
+ *   q, k_new, v_new: row (b, h) at x + b x_strides[0] + h x_strides[1], each with its own HOST stride
+ *   array (the three column blocks of the step's [B][3 H 64] q/k/v GEMM output, read in place).
+ *   k_cache, v_cache: [B][H][Lcap][64] by {batch, head, row} element strides, as k / v above.
+ *   o: [B][H][64] contiguous.  pos: a device pointer to one int32, 4-byte aligned.  The alignment
+ *   rules for everything else are those of wx_decode_attention_f32 (_h16: dtype and rules of
+ *   wx_decode_attention_h16).  workspace: wx_decode_attention_workspace_bytes(B, H, Lcap) bytes.
+ * The kernels are wx_decode_attention_f32's (one template family: the same chunks of
+ * WX_DECODE_ATTENTION_CHUNK rows, per-lane arithmetic, group merge and chunk-order merge), launched
+ * on a grid fixed by Lcap: (ceil(Lcap / 128), H, B) workgroups, of which those whose first row lies
+ * above p return at once; the lanes that own row p take it from k_new / v_new and store it to the
+ * cache, and no other workgroup touches that row.  The merge launch is enqueued whenever
+ * ceil(Lcap / 128) > 1 and returns when p < 128.  The launch function neither reads *pos nor
+ * allocates nor synchronises.
+ * B < 0, H < 1, Lcap < 1, D != 64, (h16) a dtype that is neither: WX_E_INVALID; then B == 0: WX_OK;
+ * a null or misaligned pointer (pos included), a stride that is no multiple of 4 (h16: 8), B or H
+ * above 65535: WX_E_INVALID; a short workspace: WX_E_WORKSPACE; all before anything is enqueued. */
+int wx_decode_self_attention_f32(const float* q, const float* k_new, const float* v_new, float* k_cache,
+                                 float* v_cache, float* o, int32_t B, int32_t H, int32_t Lcap, int32_t D,
+                                 const int64_t* q_strides, const int64_t* k_new_strides,
+                                 const int64_t* v_new_strides, const int64_t* k_strides, const int64_t* v_strides,
+                                 float scale, const int32_t* pos, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+int wx_decode_self_attention_h16(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache,
+                                 void* o, int32_t B, int32_t H, int32_t Lcap, int32_t D, const int64_t* q_strides,
+                                 const int64_t* k_new_strides, const int64_t* v_new_strides,
+                                 const int64_t* k_strides, const int64_t* v_strides, float scale, int32_t dtype,
+                                 const int32_t* pos, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Attention of a prompt prefill (WhisperDecoder.prefill): Tq queries per (batch, head) against Tk
  * key / value rows, under a causal mask or without one,
  *     o[b][i][h][:] = sum_j softmax_j(scale * q[b][h][i][:] . k[b][h][j][:]) v[b][h][j][:]

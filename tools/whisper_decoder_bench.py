@@ -51,6 +51,17 @@ positions, 1500 encoder positions:
     `beam_search` (--beams) from a 4-id and from a 224-id prompt, and `logits` on [16, 64], each
     with prefill=True against prefill=False in the same run.
 
+(f) --arms graph (its own record, profiles/whisper_graph_<host>.json): the graph-replayed step
+    (start / generate / beam_search with graph=True), fp32 and float16 in the same run, every figure
+    against the direct arm of the same run.  One `step` of 16 rows at position 35, direct against
+    replay (the replay arm puts the device position back with one fill_ per call, the direct arm
+    the host position); `generate` of 64 tokens x 16 chunks from a 4-id prompt, and with prefill=True
+    from a 224-id prompt; `beam_search` at --beams from the 4-id prompt; the first step of a fresh
+    plan (two warm-up passes, the capture and one replay) in ms; torch.cuda.memory_allocated with
+    the decoder alone, with a direct state and with a plan; and the self-attention launch alone at
+    L = 224 on 16 rows: wx_decode_self_attention_* against the two cache copies and
+    wx_decode_attention_* on the same q/k/v GEMM output.
+
 Prints one JSON line; --out writes it to a file (profiles/whisper_decoder_<host>.json).
 """
 from __future__ import annotations
@@ -59,6 +70,7 @@ import argparse
 import json
 import os
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
@@ -590,11 +602,148 @@ def prefill_arm(name, g, half_dtype, args, torch, F, _lib, dev):
     return r
 
 
+def graph_arm(name, g, args, torch, _lib, dev):
+    """(f) for one geometry: fp32 and float16, the direct arm and the graph arm of every figure."""
+    from transformers import WhisperConfig, WhisperForConditionalGeneration
+
+    from whisperx_amd import WhisperDecoder
+
+    D, G, H = g["D"], args.beams, g["D"] // 64
+    sync = torch.cuda.synchronize
+    eot = V - 1
+    r = {"shape": {**g, "heads": H, "vocab": V, "max_target_positions": T, "encoder_positions": P}, "beams": G}
+    cfg = WhisperConfig(d_model=D, encoder_layers=1, encoder_attention_heads=1, encoder_ffn_dim=64, num_mel_bins=80,
+                        max_source_positions=P, decoder_layers=g["layers"], decoder_attention_heads=H,
+                        decoder_ffn_dim=4 * D, vocab_size=V, max_target_positions=T, pad_token_id=0, bos_token_id=1,
+                        eos_token_id=2, decoder_start_token_id=1)
+    hf = WhisperForConditionalGeneration(cfg).eval().model.decoder
+    for p in hf.parameters():
+        p.requires_grad_(False)
+    enc = torch.randn((CHUNKS, P, D), device=dev)
+    gen = torch.Generator().manual_seed(args.seed)
+    prompts = {4: PROMPT + [50363], 224: PROMPT + torch.randint(0, 50257, (221,), generator=gen).tolist()}
+    tok = torch.full((CHUNKS,), PROMPT[0], dtype=torch.int64, device=dev)
+    for dt in (torch.float32, torch.float16):
+        label = str(dt).replace("torch.", "")
+        dec = WhisperDecoder(hf, device=dev, dtype=dt)
+        sync()
+        e = {"memory_allocated_bytes": {"decoder": torch.cuda.memory_allocated(dev)}}
+
+        # the self-attention launch alone, L = 224 on 16 rows
+        fused, plain = (_lib.decode_self_attention_f32, _lib.decode_attention_f32) if dt == torch.float32 else \
+            (_lib.decode_self_attention_h16, _lib.decode_attention_h16)
+        qkv = torch.randn((CHUNKS, 3 * D), device=dev).to(dt)
+        q, k, v = (qkv[:, j * D:(j + 1) * D].view(CHUNKS, H, 64) for j in range(3))
+        ck, cv = (torch.randn((CHUNKS, H, T, 64), device=dev).to(dt) for _ in range(2))
+        out = torch.empty((CHUNKS, H, 64), dtype=dt, device=dev)
+        pos = torch.full((1,), 223, dtype=torch.int32, device=dev)
+        ws = _lib.decode_attention_workspace(CHUNKS, H, T, dev)
+
+        def launch_fused(i):
+            return fused(q, k, v, ck, cv, pos, 0.125, out=out, workspace=ws)
+
+        def launch_copies(i):
+            ck[:, :, 223].copy_(k)
+            cv[:, :, 223].copy_(v)
+            return plain(q, ck, cv, 0.125, L=224, out=out, workspace=ws)
+
+        with torch.inference_mode():
+            a, b = launch_fused(0).clone(), launch_copies(0).clone()
+            e["self_attention_L224"] = {"rows": CHUNKS, "bit_identical": bool(torch.equal(a, b)),
+                                        "fused": event_timed(launch_fused, args.repeat, args.warmup, args.steps, torch),
+                                        "copies_and_attention": event_timed(launch_copies, args.repeat, args.warmup,
+                                                                            args.steps, torch)}
+        e["self_attention_L224"]["fused_vs_copies"] = beats(e["self_attention_L224"]["fused"],
+                                                            e["self_attention_L224"]["copies_and_attention"])
+        del qkv, q, k, v, ck, cv, out, ws
+
+        # one step of 16 rows at position 35
+        st = dec.start(enc)
+        sync()
+        e["memory_allocated_bytes"]["decoder_and_direct_state"] = torch.cuda.memory_allocated(dev)
+        for _ in range(STEP_POS):
+            dec.step(st, tok)
+
+        def step(i):
+            st.pos = STEP_POS
+            return dec._step(st, tok)
+
+        with torch.inference_mode():
+            e["step"] = {"rows": CHUNKS, "position": STEP_POS,
+                         "direct": event_timed(step, args.repeat, args.warmup, args.steps, torch)}
+        del st
+        torch.cuda.empty_cache()
+        first = []
+        for _ in range(max(1, min(3, args.repeat))):  # the first step of a fresh plan: warm-up, capture, one replay
+            dec.release_graphs()
+            torch.cuda.empty_cache()
+            gs = dec.start(enc, graph=True)
+            sync()
+            t0 = time.perf_counter()
+            dec.step(gs, tok)
+            sync()
+            first.append(time.perf_counter() - t0)
+            del gs
+        e["first_step_of_a_plan_ms"] = {"median": 1e3 * sorted(first)[len(first) // 2], "min": 1e3 * min(first),
+                                        "max": 1e3 * max(first), "repeat": len(first)}
+        gs = dec.start(enc, graph=True)
+        for _ in range(STEP_POS):
+            dec.step(gs, tok)
+        sync()
+        e["memory_allocated_bytes"]["decoder_and_plan"] = torch.cuda.memory_allocated(dev)
+
+        def replay(i):
+            gs.pos = STEP_POS
+            gs.graph.pos_dev.fill_(STEP_POS)
+            return dec._step(gs, tok)
+
+        with torch.inference_mode():
+            e["step"]["max_abs_diff_replay_vs_direct"] = float((replay(0) - step_once(dec, enc, tok, torch)).abs().max())
+            e["step"]["replay"] = event_timed(replay, args.repeat, args.warmup, args.steps, torch)
+        e["step"]["replay_vs_direct"] = beats(e["step"]["replay"], e["step"]["direct"])
+        del gs
+        print(f"{name} {label}: launch and step timed", file=sys.stderr, flush=True)
+
+        kw4 = dict(max_length=4 + N_TOKENS, suppress_tokens=[eot])
+        kw224 = dict(max_length=224 + N_TOKENS, suppress_tokens=[eot], prefill=True)
+        for what, call in (("generate_prompt_4", lambda gr: dec.generate(enc, prompts[4], eot, graph=gr, **kw4)),
+                           ("generate_prefill_224", lambda gr: dec.generate(enc, prompts[224], eot, graph=gr, **kw224)),
+                           ("beam_search_prompt_4", lambda gr: dec.beam_search(enc, prompts[4], eot, beam_size=G, graph=gr, **kw4))):
+            a, b = call(True), call(False)
+            ids = (lambda x: x) if what.startswith("generate") else (lambda x: [h[0].ids for h in x])
+            row = {"chunks": CHUNKS, "generated_tokens": N_TOKENS,
+                   "rows_with_equal_ids": sum(x == y for x, y in zip(ids(a), ids(b))) / CHUNKS,
+                   "graph": timed(lambda: call(True), args.repeat, args.warmup, sync),
+                   "direct": timed(lambda: call(False), args.repeat, args.warmup, sync)}
+            row["graph_vs_direct"] = beats(row["graph"], row["direct"])
+            e[what] = row
+            print(f"{name} {label}: {what} timed", file=sys.stderr, flush=True)
+        e["graph_captures"] = dec.graph_captures
+        r[label] = e
+        dec.release_graphs()
+        del dec
+        torch.cuda.empty_cache()
+    for what in ("generate_prompt_4", "generate_prefill_224", "beam_search_prompt_4"):
+        r[f"{what}_graph_float16_vs_float32"] = beats(r["float16"][what]["graph"], r["float32"][what]["graph"])
+    r["step_replay_float16_vs_float32"] = beats(r["float16"]["step"]["replay"], r["float32"]["step"]["replay"])
+    del hf, enc
+    return r
+
+
+def step_once(dec, enc, tok, torch):
+    """The logits of a direct state's step at STEP_POS after STEP_POS steps on `tok`."""
+    st = dec.start(enc)
+    for _ in range(STEP_POS):
+        dec.step(st, tok)
+    return dec.step(st, tok)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", default="float32", choices=["float32", "float16", "bfloat16"],
                     help="float16 / bfloat16: (d), the half route's record (profiles/whisper_decoder_half*_<host>.json)")
-    ap.add_argument("--arms", default="decoder", choices=["decoder", "beam", "prefill"], help="(a) and (b), (c), or (e)")
+    ap.add_argument("--arms", default="decoder", choices=["decoder", "beam", "prefill", "graph"],
+                    help="(a) and (b), (c), (e), or (f)")
     ap.add_argument("--beams", type=int, default=5)
     ap.add_argument("--geometries", default="base,large-v2")
     ap.add_argument("--repeat", type=int, default=5)
@@ -624,6 +773,12 @@ def main():
         for name in args.geometries.split(","):
             torch.manual_seed(args.seed)
             result["geometries"][name] = prefill_arm(name, GEOMETRIES[name], half, args, torch, F, _lib, dev)
+        args.geometries = ""
+    if args.arms == "graph":
+        result["dtype"] = ["float32", "float16"]
+        for name in args.geometries.split(","):
+            torch.manual_seed(args.seed)
+            result["geometries"][name] = graph_arm(name, GEOMETRIES[name], args, torch, _lib, dev)
         args.geometries = ""
     eot = V - 1  # suppressed: both greedy loops run their full length
     if args.dtype != "float32":

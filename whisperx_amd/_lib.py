@@ -131,6 +131,10 @@ SIGNATURES = {
                                                 _vp]),
     "wx_prefill_attention_h16": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _f32,
                                                 _i32, _vp]),
+    "wx_decode_self_attention_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
+                                                    _vp, _vp, _f32, _vp, _vp, _sz, _vp]),
+    "wx_decode_self_attention_h16": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
+                                                    _vp, _vp, _f32, _i32, _vp, _vp, _sz, _vp]),
 }
 
 
@@ -753,13 +757,14 @@ DECODE_CHUNK = 128  # WX_DECODE_ATTENTION_CHUNK (include/wx_align.h): keys per w
 
 
 def decode_attention_f32(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, L: Optional[int] = None,
-                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                         out: Optional[torch.Tensor] = None,
+                         workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """wx_decode_attention_f32: one query row per (batch, head), q [B, H, 64], against rows 0 .. L - 1
     of k / v [B, H, Lcap, 64] (L defaults to Lcap): fp32 device views of any batch / head / row
     stride with a contiguous head dim and 16-byte aligned rows, read in place (the self-attention
     cache, or the halves of the cross-attention [B, P, 2 H 64] GEMM output).  Returns [B, H, 64]
     contiguous (`out` when given) on the current stream."""
-    return _decode_attention("decode_attention_f32", q, k, v, scale, L, out, False, False)
+    return _decode_attention("decode_attention_f32", q, k, v, scale, L, out, False, False, workspace)
 
 
 DECODE_MAX_GROUP = 8  # WX_DECODE_ATTENTION_MAX_GROUP: queries per (batch, head) of the grouped kernel
@@ -767,13 +772,14 @@ BEAM_TOPK_SLICE = 4096  # WX_BEAM_TOPK_SLICE: columns per workgroup of wx_beam_t
 
 
 def decode_attention_f32_grouped(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float,
-                                 L: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                                 L: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                                 workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """wx_decode_attention_f32_grouped: G query rows per (batch, head), q [B, G, H, 64] (the beams of
     one chunk), against rows 0 .. L - 1 of the k / v [B, H, Lcap, 64] they share, read in place
     under decode_attention_f32's stride and alignment rules.  Returns [B, G, H, 64] contiguous
     (`out` when given) on the current stream; row (b, g, h) has the bits decode_attention_f32
     gives that query on the same k / v."""
-    return _decode_attention("decode_attention_f32_grouped", q, k, v, scale, L, out, False, True)
+    return _decode_attention("decode_attention_f32_grouped", q, k, v, scale, L, out, False, True, workspace)
 
 
 def beam_topk(logits: torch.Tensor, cum: torch.Tensor, G: int):
@@ -1004,8 +1010,11 @@ def add_layernorm_h16(a: torch.Tensor, b: Optional[torch.Tensor], gamma: torch.T
 
 
 def _decode_attention(who: str, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, L: Optional[int],
-                      out: Optional[torch.Tensor], half: bool, grouped: bool) -> torch.Tensor:
-    """decode_attention_f32 / _h16 (q [B, H, 64]) and their _grouped forms (q [B, G, H, 64])."""
+                      out: Optional[torch.Tensor], half: bool, grouped: bool,
+                      workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """decode_attention_f32 / _h16 (q [B, H, 64]) and their _grouped forms (q [B, G, H, 64]).
+    `workspace`: the caller's own buffer (decode_attention_workspace: a captured graph's calls must
+    not touch the shared scratch cache, which is keyed by stream and would allocate inside the capture)."""
     lib = load()
     qd = 4 if grouped else 3
     lead = "[B, G, H, 64]" if grouped else "[B, H, 64]"
@@ -1034,29 +1043,109 @@ def _decode_attention(who: str, q: torch.Tensor, k: torch.Tensor, v: torch.Tenso
     fn = getattr(lib, f"wx_decode_attention_{'h16' if half else 'f32'}{'_grouped' if grouped else ''}")
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
-        ws = _scratch.get(name, dev, getattr(lib, f"wx_{name}_workspace_bytes")(*dims), stream)
+        ws = _own_workspace(who, workspace, dev) if workspace is not None else \
+            _scratch.get(name, dev, getattr(lib, f"wx_{name}_workspace_bytes")(*dims), stream)
         _check(fn(_ptr(q), _ptr(k), _ptr(v), _ptr(out), *dims, D, st[0], st[1], st[2], float(scale),
                   *((code,) if half else ()), _ptr(ws), ws.numel(), ctypes.c_void_p(stream.cuda_stream)))
     return out
 
 
+def _own_workspace(who: str, ws: torch.Tensor, dev) -> torch.Tensor:
+    if not torch.is_tensor(ws) or ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous():
+        raise WXError(f"{who}: workspace must be a contiguous uint8 tensor on the queries' device")
+    return ws
+
+
+def decode_attention_workspace(B: int, H: int, L: int, device, G: Optional[int] = None) -> torch.Tensor:
+    """A workspace of the caller's own for the decode-attention wrappers' `workspace=` argument:
+    wx_decode_attention_workspace_bytes(B, H, L) bytes, or with `G` the grouped entry points'."""
+    lib = load()
+    n = lib.wx_decode_attention_workspace_bytes(B, H, L) if G is None else \
+        lib.wx_decode_attention_grouped_workspace_bytes(B, G, H, L)
+    return torch.empty(max(int(n), 16), dtype=torch.uint8, device=device)
+
+
+def _decode_self_attention(who: str, q, k_new, v_new, k_cache, v_cache, pos, scale, out, workspace, half: bool):
+    """decode_self_attention_f32 and decode_self_attention_h16."""
+    lib = load()
+    if q.dim() != 3 or k_cache.dim() != 4 or v_cache.dim() != 4:
+        raise WXError(f"{who}: q {tuple(q.shape)} / k_cache {tuple(k_cache.shape)} / v_cache {tuple(v_cache.shape)} are "
+                      "not [B, H, 64] / [B, H, Lcap, 64] / [B, H, Lcap, 64]")
+    B, H, D = (int(x) for x in q.shape)
+    Lcap = int(k_cache.shape[2])
+    if tuple(k_new.shape) != (B, H, D) or tuple(v_new.shape) != (B, H, D) or tuple(k_cache.shape) != (B, H, Lcap, D) or \
+            tuple(v_cache.shape) != (B, H, Lcap, D) or Lcap < 1:
+        raise WXError(f"{who}: k_new {tuple(k_new.shape)} / v_new {tuple(v_new.shape)} / k_cache {tuple(k_cache.shape)} / "
+                      f"v_cache {tuple(v_cache.shape)} do not fit q {tuple(q.shape)}")
+    dev = q.device
+    code = HALF_DTYPES.get(q.dtype) if half else None
+    for t in (q, k_new, v_new, k_cache, v_cache):
+        if (code is None if half else t.dtype != torch.float32) or t.dtype != q.dtype or not t.is_cuda or \
+                t.device != dev or t.stride(-1) != 1:
+            raise WXError(f"{who}: q, k_new, v_new and the caches must "
+                          f"{'share one of float16 / bfloat16' if half else 'be float32 tensors'}, on one HIP device with "
+                          "a contiguous head dim")
+    if not torch.is_tensor(pos) or pos.dtype != torch.int32 or pos.numel() != 1 or pos.device != dev:
+        raise WXError(f"{who}: pos must be an int32 tensor of one element on the queries' device")
+    if out is None:
+        out = torch.empty((B, H, D), dtype=q.dtype, device=dev)
+    if tuple(out.shape) != (B, H, D) or out.dtype != q.dtype or out.device != dev or not out.is_contiguous():
+        raise WXError(f"{who}: out must be a contiguous [B, H, 64] tensor of the queries' dtype on their device")
+    st = [(ctypes.c_int64 * n)(*(int(x) for x in t.stride()[:n]))
+          for t, n in ((q, 2), (k_new, 2), (v_new, 2), (k_cache, 3), (v_cache, 3))]
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        ws = _own_workspace(who, workspace, dev) if workspace is not None else \
+            _scratch.get("decode_attention", dev, lib.wx_decode_attention_workspace_bytes(B, H, Lcap), stream)
+        _check(getattr(lib, "wx_" + who)(_ptr(q), _ptr(k_new), _ptr(v_new), _ptr(k_cache), _ptr(v_cache), _ptr(out), B, H,
+                                         Lcap, D, *st, float(scale), *((code,) if half else ()), _ptr(pos), _ptr(ws),
+                                         ws.numel(), ctypes.c_void_p(stream.cuda_stream)))
+    return out
+
+
+def decode_self_attention_f32(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor,
+                              v_cache: torch.Tensor, pos: torch.Tensor, scale: float,
+                              out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """wx_decode_self_attention_f32: the self-attention of one decode step at the position p = pos[0]
+    that the kernels read on the device (`pos`: an int32 device tensor of one element).  q / k_new /
+    v_new [B, H, 64] are fp32 device views (the column blocks of the q/k/v GEMM output as they are),
+    k_cache / v_cache [B, H, Lcap, 64]: row p of the caches becomes k_new / v_new, and the result
+    [B, H, 64] (`out` when given) has the bits of decode_attention_f32 with L = p + 1 on the caches
+    after that copy.  p outside [0, Lcap) writes nothing.  The launch does not depend on p, so a
+    captured graph may replay it; pass the graph's own `workspace` (decode_attention_workspace(B, H,
+    Lcap)) then.  On the current stream."""
+    return _decode_self_attention("decode_self_attention_f32", q, k_new, v_new, k_cache, v_cache, pos, scale, out,
+                                  workspace, False)
+
+
+def decode_self_attention_h16(q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tensor,
+                              v_cache: torch.Tensor, pos: torch.Tensor, scale: float,
+                              out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """wx_decode_self_attention_h16: decode_self_attention_f32 on fp16 or bf16 tensors of one dtype,
+    under decode_attention_h16's stride rules; the result has decode_attention_h16's bits at L = p + 1."""
+    return _decode_self_attention("decode_self_attention_h16", q, k_new, v_new, k_cache, v_cache, pos, scale, out,
+                                  workspace, True)
+
+
 def decode_attention_h16(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, L: Optional[int] = None,
-                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                         out: Optional[torch.Tensor] = None,
+                         workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """wx_decode_attention_h16: decode_attention_f32 on fp16 or bf16 device views of one dtype: q
     [B, H, 64] against rows 0 .. L - 1 of k / v [B, H, Lcap, 64], read in place (head dim contiguous,
     every other stride a multiple of 8 elements, 16-byte aligned).  Returns [B, H, 64] contiguous in
     that dtype (`out` when given) on the current stream: decode_attention_f32 of the widened inputs,
     rounded once."""
-    return _decode_attention("decode_attention_h16", q, k, v, scale, L, out, True, False)
+    return _decode_attention("decode_attention_h16", q, k, v, scale, L, out, True, False, workspace)
 
 
 def decode_attention_h16_grouped(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float,
-                                 L: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                                 L: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                                 workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """wx_decode_attention_h16_grouped: G query rows per (batch, head), q [B, G, H, 64] fp16 or bf16,
     against the k / v [B, H, Lcap, 64] they share, under decode_attention_h16's rules.  Returns
     [B, G, H, 64] contiguous in that dtype; row (b, g, h) has the bits decode_attention_h16 gives that
     query on the same k / v."""
-    return _decode_attention("decode_attention_h16_grouped", q, k, v, scale, L, out, True, True)
+    return _decode_attention("decode_attention_h16_grouped", q, k, v, scale, L, out, True, True, workspace)
 
 
 def _prefill_attention(who: str, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, causal: Optional[int],

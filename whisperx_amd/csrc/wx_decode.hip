@@ -5,7 +5,7 @@
 // of the cross-attention [B, P, 2D] GEMM output).  fp32, and fp16 / bf16 (whisperx/asr.py:262: the
 // reference loads its model with compute_type="float16", which covers the decoder's key / value
 // caches and the cross-attention keys and values).  C ABI and semantics: include/wx_align.h
-// (wx_decode_attention_f32, _f32_grouped, _h16, _h16_grouped).
+// (wx_decode_attention_f32, _f32_grouped, _h16, _h16_grouped, wx_decode_self_attention_f32, _h16).
 //
 // The work is a read of 2 L rows of 256 (16-bit: 128) bytes per (batch, head) and nothing else, so
 // the key range is split over workgroups ("flash-decoding"):
@@ -168,25 +168,16 @@ __device__ __forceinline__ void merge_groups(const float* gm, const float* gl, c
     }
 }
 
+// A block's rows to its result, for the kernels of one query per (batch, head): the 16 groups'
+// partials of the n rows in kr / vr, merged through LDS in group order by wave 0, which writes
+// o = acc / l when the keys are one chunk (nc == 1) and the chunk's slot of the workspace otherwise.
 template <int ET>
-__global__ __launch_bounds__(256) void decode_chunk_kernel(const DecArgs a) {
-    typedef elem_t<ET> elem;
+__device__ __forceinline__ void chunk_result(const DecArgs& a, const row_t<ET> qr, const row_t<ET> (&kr)[kPasses],
+                                             const row_t<ET> (&vr)[kPasses], int b, int h, int c, int n, int nc) {
     __shared__ float s_m[kGroups], s_l[kGroups];
     __shared__ __attribute__((aligned(16))) float s_acc[kGroups][kHead];
-    const int c = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
     const int tid = threadIdx.x;
     const int grp = tid >> 4, d4 = (tid & 15) * 4;
-    const int j0 = c * kChunk;            // (< L <= 2^31 - 1)
-    const int n = min(kChunk, a.L - j0);  // rows of this chunk, >= 1
-
-    const row_t<ET> qr = *reinterpret_cast<const row_t<ET>*>(static_cast<const elem*>(a.q) + (int64_t)b * a.qs[0] +
-                                                              (int64_t)h * a.qs[1] + d4);
-    const elem* kb = rows_at<ET>(a.k, a.ks, b, h, j0, d4);
-    const elem* vb = rows_at<ET>(a.v, a.vs, b, h, j0, d4);
-    row_t<ET> kr[kPasses], vr[kPasses];
-    load_rows<ET>(kb, a.ks[2], grp, n, kr);
-    load_rows<ET>(vb, a.vs[2], grp, n, vr);
-
     float m, l;
     float4 acc;
     group_partial<ET>(widen4<ET>(qr), kr, vr, grp, n, a.scale, m, l, acc);
@@ -201,33 +192,118 @@ __global__ __launch_bounds__(256) void decode_chunk_kernel(const DecArgs a) {
     float M, Lsum, out;  // wave 0, lane = dim
     merge_groups(s_m, s_l, &s_acc[0][0], tid, M, Lsum, out);
     const int64_t bh = (int64_t)b * a.H + h;
-    if (a.nc == 1) {
-        static_cast<elem*>(a.o)[bh * kHead + tid] = narrow<ET>(out / Lsum);
+    if (nc == 1) {
+        static_cast<elem_t<ET>*>(a.o)[bh * kHead + tid] = narrow<ET>(out / Lsum);
         return;
     }
-    const int64_t slot = bh * a.nc + c;
+    const int64_t slot = bh * nc + c;
     if (tid == 0) a.ml[slot] = make_float2(M, Lsum);
     a.acc[slot * kHead + tid] = out;
 }
 
-// one wave per (batch, head), lane = dim: the chunks in chunk order
+// Row (b, h) of q (or of the step's new key / value rows) by its strides {b, h}, the lane's 4 dims
 template <int ET>
-__global__ __launch_bounds__(256) void decode_merge_kernel(const DecArgs a, int64_t BH) {
-    const int64_t bh = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int d = threadIdx.x & 63;
-    if (bh >= BH) return;
-    const float2* ml = a.ml + bh * a.nc;
-    const float* acc = a.acc + bh * a.nc * kHead;
+__device__ __forceinline__ row_t<ET> row_of(const void* p, const int64_t* s, int b, int h, int d4) {
+    return *reinterpret_cast<const row_t<ET>*>(static_cast<const elem_t<ET>*>(p) + (int64_t)b * s[0] + (int64_t)h * s[1] +
+                                               d4);
+}
+
+template <int ET>
+__global__ __launch_bounds__(256) void decode_chunk_kernel(const DecArgs a) {
+    const int c = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+    const int grp = threadIdx.x >> 4, d4 = (threadIdx.x & 15) * 4;
+    const int j0 = c * kChunk;            // (< L <= 2^31 - 1)
+    const int n = min(kChunk, a.L - j0);  // rows of this chunk, >= 1
+
+    const row_t<ET> qr = row_of<ET>(a.q, a.qs, b, h, d4);
+    row_t<ET> kr[kPasses], vr[kPasses];
+    load_rows<ET>(rows_at<ET>(a.k, a.ks, b, h, j0, d4), a.ks[2], grp, n, kr);
+    load_rows<ET>(rows_at<ET>(a.v, a.vs, b, h, j0, d4), a.vs[2], grp, n, vr);
+    chunk_result<ET>(a, qr, kr, vr, b, h, c, n, a.nc);
+}
+
+// one (batch, head) of a wave, lane d = dim: its nc chunks in chunk order
+template <int ET>
+__device__ __forceinline__ void merge_chunks(const DecArgs& a, int64_t bh, int nc, int d) {
+    const float2* ml = a.ml + bh * nc;
+    const float* acc = a.acc + bh * nc * kHead;
     float M = -INFINITY;
-    for (int c = 0; c < a.nc; ++c) M = fmaxf(M, ml[c].x);
+    for (int c = 0; c < nc; ++c) M = fmaxf(M, ml[c].x);
     float Lsum = 0.f, out = 0.f;
-    for (int c = 0; c < a.nc; ++c) {
+    for (int c = 0; c < nc; ++c) {
         const float2 p = ml[c];
         const float w = expf(p.x - M);
         Lsum += w * p.y;
         out += w * acc[(int64_t)c * kHead + d];
     }
     static_cast<elem_t<ET>*>(a.o)[bh * kHead + d] = narrow<ET>(out / Lsum);
+}
+
+// one wave per (batch, head), lane = dim: the chunks in chunk order
+template <int ET>
+__global__ __launch_bounds__(256) void decode_merge_kernel(const DecArgs a, int64_t BH) {
+    const int64_t bh = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (bh >= BH) return;
+    merge_chunks<ET>(a, bh, a.nc, threadIdx.x & 63);
+}
+
+// ------------------------------------------------------------------------------ self
+// The self-attention of one decode step at a position that lives in device memory
+// (wx_decode_self_attention_f32 / _h16): p = *pos is read by the kernels, so that the launch is the
+// same at every step and a captured graph can replay it.  The grid covers the cache's Lcap rows; a
+// block whose first row lies above p returns at once, the others are decode_chunk_kernel's blocks at
+// L = p + 1 (same load_rows, chunk_result and slots, nc = p / 128 + 1 computed here), except that
+// row p comes from the step's new key / value rows, not from the cache: load_rows stops below it,
+// the lanes of its group and pass take it from k_new / v_new and store it to the cache.  Only the
+// block that owns row p touches it, so there is no hand-shake.  The merge kernel reads p the same
+// way and returns when one chunk block has written o itself.  p outside [0, Lcap): every block of
+// both kernels returns before it reads or writes anything else.
+struct SelfArgs {
+    DecArgs d;  // k / v: the caches (written at row p); L: Lcap; nc: chunks(Lcap), the grid's x
+    const void *kn, *vn;  // elem_t<ET>: the new rows, by {b, h} strides
+    int64_t kns[2], vns[2];
+    const int32_t* pos;
+};
+
+template <int ET>
+__global__ __launch_bounds__(256) void decode_self_chunk_kernel(const SelfArgs s) {
+    typedef elem_t<ET> elem;
+    const DecArgs& a = s.d;
+    const int c = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+    const int grp = threadIdx.x >> 4, d4 = (threadIdx.x & 15) * 4;
+    const int p = *s.pos;
+    const int j0 = c * kChunk;  // (< Lcap)
+    if (p < 0 || p >= a.L || j0 > p) return;
+    const int n = min(kChunk, p + 1 - j0);       // rows of this chunk at L = p + 1, >= 1
+    const int fresh = p - j0 < kChunk ? p - j0 : -1;  // row p's place in this chunk (then n - 1), or none
+    const int cached = fresh < 0 ? n : fresh;    // the rows the cache holds
+
+    const row_t<ET> qr = row_of<ET>(a.q, a.qs, b, h, d4);
+    const elem* kb = rows_at<ET>(a.k, a.ks, b, h, j0, d4);
+    const elem* vb = rows_at<ET>(a.v, a.vs, b, h, j0, d4);
+    row_t<ET> kr[kPasses], vr[kPasses];
+    load_rows<ET>(kb, a.ks[2], grp, cached, kr);
+    load_rows<ET>(vb, a.vs[2], grp, cached, vr);
+    if (fresh >= 0 && (fresh & (kGroups - 1)) == grp) {  // the 16 lanes that hold row p
+        const row_t<ET> kn = row_of<ET>(s.kn, s.kns, b, h, d4), vn = row_of<ET>(s.vn, s.vns, b, h, d4);
+#pragma unroll
+        for (int i = 0; i < kPasses; ++i)
+            if (i == fresh / kGroups) {
+                kr[i] = kn;
+                vr[i] = vn;
+            }
+        *reinterpret_cast<row_t<ET>*>(const_cast<elem*>(kb) + (int64_t)fresh * a.ks[2]) = kn;
+        *reinterpret_cast<row_t<ET>*>(const_cast<elem*>(vb) + (int64_t)fresh * a.vs[2]) = vn;
+    }
+    chunk_result<ET>(a, qr, kr, vr, b, h, c, n, p / kChunk + 1);
+}
+
+template <int ET>
+__global__ __launch_bounds__(256) void decode_self_merge_kernel(const SelfArgs s, int64_t BH) {
+    const int64_t bh = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int p = *s.pos;
+    if (bh >= BH || p < kChunk || p >= s.d.L) return;  // (p < 128: one chunk, whose block wrote o)
+    merge_chunks<ET>(s.d, bh, p / kChunk + 1, threadIdx.x & 63);
 }
 
 // ------------------------------------------------------------------------------ grouped
@@ -366,6 +442,71 @@ inline int run(int32_t et, bool grouped, const void* q, const void* k, const voi
     return wx::launch_status();
 }
 
+template <int ET>
+void launch_self(const SelfArgs& s, int32_t B, hipStream_t st) {
+    const DecArgs& a = s.d;
+    hipLaunchKernelGGL(decode_self_chunk_kernel<ET>, dim3((unsigned)a.nc, (unsigned)a.H, (unsigned)B), dim3(256), 0, st, s);
+    if (a.nc > 1) {
+        const int64_t BH = (int64_t)B * a.H;
+        hipLaunchKernelGGL(decode_self_merge_kernel<ET>, dim3((unsigned)((BH + 3) / 4)), dim3(256), 0, st, s, BH);
+    }
+}
+
+// The two self-attention entry points: the checks in the header's order, then the launches, which
+// depend on Lcap only.  Nothing here reads *pos, allocates or synchronises.
+inline int run_self(int32_t et, const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache,
+                    void* o, int32_t B, int32_t H, int32_t Lcap, int32_t D, const int64_t* q_strides,
+                    const int64_t* kn_strides, const int64_t* vn_strides, const int64_t* k_strides,
+                    const int64_t* v_strides, float scale, const int32_t* pos, void* workspace, size_t workspace_bytes,
+                    void* stream) {
+    if (B < 0 || H < 1 || Lcap < 1 || D != kHead || (et != kF32 && et != kF16 && et != kBF16)) return WX_E_INVALID;
+    if (B == 0) return WX_OK;
+    if (!q || !k_new || !v_new || !k_cache || !v_cache || !o || !pos || !q_strides || !kn_strides || !vn_strides ||
+        !k_strides || !v_strides || !workspace)
+        return WX_E_INVALID;
+    for (const void* p : {q, k_new, v_new, (const void*)k_cache, (const void*)v_cache, (const void*)o,
+                          (const void*)workspace})
+        if (reinterpret_cast<uintptr_t>(p) & 15) return WX_E_INVALID;
+    if (reinterpret_cast<uintptr_t>(pos) & 3) return WX_E_INVALID;
+    const int mult = et == kF32 ? 4 : 8;
+    for (int i = 0; i < 2; ++i)
+        if (q_strides[i] % mult || kn_strides[i] % mult || vn_strides[i] % mult) return WX_E_INVALID;
+    for (int i = 0; i < 3; ++i)
+        if (k_strides[i] % mult || v_strides[i] % mult) return WX_E_INVALID;
+    if (B > 65535 || H > 65535) return WX_E_INVALID;  // grid y / z
+    if ((int64_t)B * H * chunks(Lcap) > ((int64_t)1 << 40)) return WX_E_INVALID;
+    SelfArgs s;
+    DecArgs& a = s.d;
+    if (workspace_bytes < carve(workspace, B, H, Lcap, &a)) return WX_E_WORKSPACE;
+    a.q = q;
+    a.k = k_cache;
+    a.v = v_cache;
+    a.o = o;
+    s.kn = k_new;
+    s.vn = v_new;
+    s.pos = pos;
+    a.qs[2] = 0;
+    for (int i = 0; i < 2; ++i) {
+        a.qs[i] = q_strides[i];
+        s.kns[i] = kn_strides[i];
+        s.vns[i] = vn_strides[i];
+    }
+    for (int i = 0; i < 3; ++i) {
+        a.ks[i] = k_strides[i];
+        a.vs[i] = v_strides[i];
+    }
+    a.H = H;
+    a.L = Lcap;
+    a.nc = (int32_t)chunks(Lcap);
+    a.G = 1;
+    a.scale = scale;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (et == kF32) launch_self<kF32>(s, B, st);
+    else if (et == kF16) launch_self<kF16>(s, B, st);
+    else launch_self<kBF16>(s, B, st);
+    return wx::launch_status();
+}
+
 // a dtype argument that is no 16-bit type must not pass for kF32
 inline int32_t et_of(int32_t dtype) { return dtype == WX_DTYPE_F16 || dtype == WX_DTYPE_BF16 ? dtype : -1; }
 
@@ -410,4 +551,25 @@ extern "C" int wx_decode_attention_h16_grouped(const void* q, const void* k, con
                                                int32_t dtype, void* workspace, size_t workspace_bytes, void* stream) {
     return wxdec::run(wxdec::et_of(dtype), true, q, k, v, o, B, G, H, L, D, q_strides, k_strides, v_strides, scale,
                       workspace, workspace_bytes, stream);
+}
+
+extern "C" int wx_decode_self_attention_f32(const float* q, const float* k_new, const float* v_new, float* k_cache,
+                                            float* v_cache, float* o, int32_t B, int32_t H, int32_t Lcap, int32_t D,
+                                            const int64_t* q_strides, const int64_t* k_new_strides,
+                                            const int64_t* v_new_strides, const int64_t* k_strides,
+                                            const int64_t* v_strides, float scale, const int32_t* pos, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+    return wxdec::run_self(wxdec::kF32, q, k_new, v_new, k_cache, v_cache, o, B, H, Lcap, D, q_strides, k_new_strides,
+                           v_new_strides, k_strides, v_strides, scale, pos, workspace, workspace_bytes, stream);
+}
+
+extern "C" int wx_decode_self_attention_h16(const void* q, const void* k_new, const void* v_new, void* k_cache,
+                                            void* v_cache, void* o, int32_t B, int32_t H, int32_t Lcap, int32_t D,
+                                            const int64_t* q_strides, const int64_t* k_new_strides,
+                                            const int64_t* v_new_strides, const int64_t* k_strides,
+                                            const int64_t* v_strides, float scale, int32_t dtype, const int32_t* pos,
+                                            void* workspace, size_t workspace_bytes, void* stream) {
+    return wxdec::run_self(wxdec::et_of(dtype), q, k_new, v_new, k_cache, v_cache, o, B, H, Lcap, D, q_strides,
+                           k_new_strides, v_new_strides, k_strides, v_strides, scale, pos, workspace, workspace_bytes,
+                           stream);
 }

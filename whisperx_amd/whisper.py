@@ -42,6 +42,12 @@ beam_search / logits with prefill=True): the same layers on [B n, D] rows, with
 wx_prefill_attention_f32 for the n queries against the cache under a causal mask and against
 K_x / V_x.  Temperature fallback, timestamps and the tokenizer are not built.
 
+With `graph=True` (start, generate, beam_search, logits; off by default, HIP route only) a step is
+one replay of a captured graph: the self-attention is wx_decode_self_attention_f32 (_h16), which
+reads the position from device memory and appends the cache row itself, the positional row is an
+index_select by that device position, and the graph's last node adds 1 to it.  The graph and its
+static tensors are a plan the decoder keeps per (B, G, P) and hands to the next state of that shape.
+
 With `dtype` float16 or bfloat16 the decoder runs the reference's compute type too (asr.py:262).
 Rounded to dtype: the GEMMs (weights and biases once, at construction; q/k/v, out, fc1, fc2 and the
 cross-attention k/v GEMM of start()), the GELU, both attentions with the self-attention caches and
@@ -60,7 +66,9 @@ Without a GPU the same arithmetic runs in torch ops on the host (`F.conv1d`, `F.
 """
 from __future__ import annotations
 
+import collections
 import contextlib
+import gc
 import re
 import weakref
 from typing import NamedTuple, Optional
@@ -73,6 +81,7 @@ from . import _lib
 from .audio import log_mel_chunks
 
 _LN_EPS = 1e-5
+_MAX_PLANS = 2  # graph plans a WhisperDecoder keeps (start(graph=True))
 _MAX_BEAMS = _lib.DECODE_MAX_GROUP  # beams per chunk: the group size of wx_decode_attention_f32_grouped / wx_beam_topk
 
 
@@ -446,7 +455,9 @@ class DecoderState:
     `stages`: the decoder's layers bound to these tensors, built at the first step.  With `G` > 1
     beams per chunk (`start(beams=G)`) there are `rows` = B G sequences, row b G + g beam g of chunk
     b: the caches are [B G, H, max_target_positions, 64] and `cross` stays [B, P, 2D], shared by a
-    chunk's beams.  `cross` and the caches have the decoder's dtype."""
+    chunk's beams.  `cross` and the caches have the decoder's dtype.  `graph`: the _GraphPlan of a
+    state from `start(graph=True)` (its tensors are the plan's; `pos` is then the host mirror of the
+    plan's device position), else None."""
 
     def __init__(self, B: int, P: int, cross, self_k, self_v, kernels: bool, beams: int = 1):
         self.B, self.P, self.pos = B, P, 0
@@ -454,6 +465,36 @@ class DecoderState:
         self.cross, self.self_k, self.self_v = cross, self_k, self_v
         self.kernels = kernels
         self.stages = None
+        self.graph = None
+
+
+class _GraphPlan:
+    """What a graph-replayed decode step owns, kept by the decoder per (B, G, P): the static tensors
+    (the state's `cross` and caches, `pos_dev` int32 [1], the token buffer `tok` [rows] int64, the
+    logits buffer [rows, V] fp32, the attention workspaces), the stages bound to them, and the
+    captured step graph (`graph`, None until the first step).  `owner`: a weak reference to the state
+    the plan is bound to; the plan is free again when that state is gone.  For greedy decoding
+    (G = 1) also what the device-side selection needs, and its small graph `select`: `suppress`
+    [V] bool (the ids at -inf), `eot` int64 [1], `done` [rows] bool, `count` int64 [1] (generated
+    steps so far) and `record` [max_target_positions, rows] int64 (the ids of every step)."""
+
+    def __init__(self, dec: "WhisperDecoder", B: int, G: int, P: int):
+        dev, dt, R = dec.device, dec.dtype, B * G
+        shape = (R, dec.H, dec.max_target_positions, 64)
+        self.key = (B, G, P)
+        self.cross = [torch.empty((B, P, 2 * dec.D), dtype=dt, device=dev) for _ in dec.layers]
+        self.self_k = [torch.zeros(shape, dtype=dt, device=dev) for _ in dec.layers]
+        self.self_v = [torch.zeros(shape, dtype=dt, device=dev) for _ in dec.layers]
+        self.pos_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.tok = torch.zeros(R, dtype=torch.int64, device=dev)
+        self.logits = torch.empty((R, dec.V), dtype=torch.float32, device=dev)
+        self.ws_self = _lib.decode_attention_workspace(R, dec.H, dec.max_target_positions, dev)
+        self.ws_cross = _lib.decode_attention_workspace(B, dec.H, P, dev, G if G > 1 else None)
+        self.stages = None
+        self.graph = None
+        self.owner = lambda: None
+        self.select = None
+        self.suppress = self.eot = self.done = self.count = self.record = None
 
 
 class WhisperDecoder:
@@ -511,13 +552,16 @@ class WhisperDecoder:
             L["fc1"], L["fc2"] = take.mlp(p, D)
             self.layers.append(L)
         self.ln_f = take.pair("layer_norm", D)
+        self._plans = collections.OrderedDict()  # (B, G, P) -> _GraphPlan, least recently used first
+        self.graph_captures = 0  # step graphs captured so far (one per plan)
 
     # --------------------------------------------------------------------------------- steps
     def _ctx(self):
         return torch.cuda.device(self.device) if self.device.type == "cuda" else contextlib.nullcontext()
 
     @torch.inference_mode()
-    def start(self, encoder_states: torch.Tensor, kernels: Optional[bool] = None, beams: int = 1) -> DecoderState:
+    def start(self, encoder_states: torch.Tensor, kernels: Optional[bool] = None, beams: int = 1,
+              graph: bool = False) -> DecoderState:
         """encoder_states [B, P, D] (WhisperEncoder.encode's output) -> the state of a batch of B
         sequences at position 0: per layer one GEMM with [Wk_x; Wv_x] gives the cross-attention
         keys and values [B, P, 2D], which every step then reads in place, and the self-attention
@@ -525,7 +569,16 @@ class WhisperDecoder:
         default on a HIP device) or the same arithmetic in torch ops on the decoder's device.
         `beams` = G > 1: B G sequences, G per chunk (row b G + g), for beam search: the caches
         have B G rows, the cross-attention keys and values stay [B, P, 2D] and a chunk's G beams
-        read them through wx_decode_attention_f32_grouped (an expanded view on the host route)."""
+        read them through wx_decode_attention_f32_grouped (an expanded view on the host route).
+        `graph`: every `step` of the state is one replay of a captured graph (HIP route only, else
+        ValueError; both dtypes, any `beams`).  The state's tensors are then those of a plan that
+        the decoder keeps per (B, G, P), at most two plans, the least recently used dropped first:
+        a start of a known shape refills the plan's cross-attention tensors and resets its device
+        position, and nothing is captured again (`graph_captures` counts the step graphs captured
+        so far).  The caches are not cleared: rows at and above the position are never read.  A
+        plan is bound to one live state: while that state exists, a start of its shape builds
+        another plan, which takes the first one's place in the decoder's list (the first lives on
+        with its state).  `release_graphs()` drops the decoder's plans."""
         beams = int(beams)
         if not 1 <= beams <= _MAX_BEAMS:
             raise ValueError(f"WhisperDecoder.start: beams must lie in 1..{_MAX_BEAMS}, got {beams}")
@@ -536,14 +589,41 @@ class WhisperDecoder:
         kernels = self.device.type == "cuda" if kernels is None else bool(kernels)
         if kernels and self.device.type != "cuda":
             raise ValueError("WhisperDecoder.start: the HIP route needs the decoder on a HIP device")
+        if graph and not kernels:
+            raise ValueError("WhisperDecoder.start: graph=True replays HIP kernels and needs the HIP route; this state "
+                             f"is on the torch route (kernels=False, decoder on '{self.device}')")
         x = x.to(device=self.device, dtype=self.dtype)
         B, P = int(x.shape[0]), int(x.shape[1])
+        if graph:
+            return self._start_graph(x, B, P, beams)
         with self._ctx():
             cross = [F.linear(x, *L["kv_x"]) for L in self.layers]
             shape = (B * beams, self.H, self.max_target_positions, 64)
             self_k = [torch.zeros(shape, dtype=self.dtype, device=self.device) for _ in self.layers]
             self_v = [torch.zeros(shape, dtype=self.dtype, device=self.device) for _ in self.layers]
         return DecoderState(B, P, cross, self_k, self_v, kernels, beams)
+
+    def _start_graph(self, x: torch.Tensor, B: int, P: int, G: int) -> DecoderState:
+        """start(graph=True) on the checked encoder states: a free plan of this shape, or a new one."""
+        key = (B, G, P)
+        with self._ctx():
+            plan = self._plans.get(key)
+            if plan is None or plan.owner() is not None:
+                plan = self._plans[key] = _GraphPlan(self, B, G, P)
+            self._plans.move_to_end(key)
+            while len(self._plans) > _MAX_PLANS:
+                self._plans.popitem(last=False)
+            for c, L in zip(plan.cross, self.layers):
+                c.copy_(F.linear(x, *L["kv_x"]))
+            plan.pos_dev.zero_()
+        st = DecoderState(B, P, plan.cross, plan.self_k, plan.self_v, True, G)
+        st.graph, plan.owner = plan, weakref.ref(st)
+        return st
+
+    def release_graphs(self) -> None:
+        """Drops the plans the decoder keeps for `start(graph=True)`: their tensors and graphs are
+        freed once no state uses them.  A later start captures again."""
+        self._plans.clear()
 
     def _tokens(self, tokens, shape, who: str) -> torch.Tensor:
         """Token ids as an int64 tensor of `shape` on the decoder's device, every id in [0, V)."""
@@ -559,7 +639,12 @@ class WhisperDecoder:
     def step(self, state: DecoderState, tokens) -> torch.Tensor:
         """One position for every row: tokens [B] (ids at position state.pos; [B G] for a state of
         G beams) -> the logits of the next token [B, V] fp32 ([B G, V]), and the state moves on by
-        one.  Runs on the current stream."""
+        one.  Runs on the current stream.  On a state from `start(graph=True)` the first step
+        runs the step's kernels directly (twice, as a warm-up: without the position's increment the
+        step only rewrites cache row `pos` with the same values) and captures them as one linear
+        graph whose last node adds 1 to the device position; that step and every later one is a
+        copy of `tokens` into the plan's token buffer and one replay.  It returns the plan's logits
+        buffer, which is valid until the next step of the state."""
         return self._step(state, self._tokens(tokens, (state.rows,), "step"))
 
     def _step(self, st: DecoderState, tok: torch.Tensor) -> torch.Tensor:
@@ -567,6 +652,8 @@ class WhisperDecoder:
         if st.pos >= self.max_target_positions:
             raise ValueError(f"WhisperDecoder.step: position {st.pos} is past max_target_positions "
                              f"({self.max_target_positions})")
+        if st.graph is not None:
+            return self._graph_step(st, tok)
         if st.stages is None:  # once per state: the step path only calls them
             st.stages = self._stages(weakref.proxy(st))  # (a proxy: the state owns its stages, not they it)
         with self._ctx():
@@ -579,6 +666,105 @@ class WhisperDecoder:
             y = _chain(h, st.stages, self.ln_f, _lib.add_layernorm if st.kernels else None)
             st.pos += 1
             return F.linear(y, self.embed)
+
+    def _graph_step(self, st: DecoderState, tok: Optional[torch.Tensor]) -> torch.Tensor:
+        """_step on a graph state (the position already checked on the host mirror): the ids into
+        the plan's token buffer (None: they are there), then one replay."""
+        plan = st.graph
+        with self._ctx():
+            if tok is not None:
+                plan.tok.copy_(tok)
+            if plan.graph is None:
+                self._capture(plan)
+            plan.graph.replay()
+        st.pos += 1
+        return plan.logits
+
+    def _graph_body(self, plan: _GraphPlan) -> None:
+        """One step on the plan's tensors at the position in plan.pos_dev, which it leaves as it
+        is: _step's arithmetic, the position read on the device."""
+        half = self.dtype != torch.float32
+        e = F.embedding(plan.tok, self.embed)
+        h = (e.float() if half else e) + self.pos.index_select(0, plan.pos_dev)
+        if half:
+            y = _chain_half(h, plan.stages, self.ln_f, self.dtype, True)
+            plan.logits.copy_(F.linear(y.to(self.dtype), self.embed))
+        else:
+            plan.logits.copy_(F.linear(_chain(h, plan.stages, self.ln_f, _lib.add_layernorm), self.embed))
+
+    @staticmethod
+    def _warm_up(device, body) -> None:
+        """`body` once on a side stream, ordered after and before the current one: what torch asks
+        for before a capture (libraries initialised, kernels loaded)."""
+        cur, side = torch.cuda.current_stream(device), torch.cuda.Stream(device)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            body()
+        cur.wait_stream(side)
+
+    @staticmethod
+    @contextlib.contextmanager
+    def _capturing(g):
+        """torch.cuda.graph(g) with Python's cyclic collector run before it and held off during it:
+        a graph object that the collector frees while a stream is capturing (one left in a dead
+        reference cycle by anyone) makes a HIP call that is illegal then, and its destructor ends
+        the process."""
+        gc.collect()
+        was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(g):
+                yield
+        finally:
+            if was_on:
+                gc.enable()
+
+    def _capture(self, plan: _GraphPlan) -> None:
+        """The plan's step graph: body, then pos_dev += 1, one linear chain on the capture stream."""
+        if plan.stages is None:  # (a proxy: the plan owns its stages, not they it, so it dies by reference count)
+            plan.stages = self._graph_stages(weakref.proxy(plan))
+        self._warm_up(self.device, lambda: (self._graph_body(plan), self._graph_body(plan)))
+        g = torch.cuda.CUDAGraph()
+        with self._capturing(g):
+            self._graph_body(plan)
+            plan.pos_dev.add_(1)
+        plan.graph = g
+        self.graph_captures += 1
+
+    def _graph_stages(self, plan: _GraphPlan) -> list:
+        """_stages on a plan's tensors for the graph: the self-attention is one call of
+        wx_decode_self_attention_f32 (_h16) on the q/k/v GEMM output, which reads the position on
+        the device and appends the cache row itself; the cross-attention is _stages' (its L = P is
+        a constant).  Every call uses the plan's workspaces."""
+        B, G, P = plan.key
+        R, D, H = B * G, self.D, self.H
+        half = self.dtype != torch.float32
+        attend_self = _lib.decode_self_attention_h16 if half else _lib.decode_self_attention_f32
+        one = _lib.decode_attention_h16 if half else _lib.decode_attention_f32
+        grouped = _lib.decode_attention_h16_grouped if half else _lib.decode_attention_f32_grouped
+
+        def self_attention(L, ck, cv):
+            def fn(y):
+                qkv = F.linear(y, *L["qkv"])  # [R, 3D]
+                q, k, v = (qkv[:, j * D:(j + 1) * D].view(R, H, 64) for j in range(3))
+                o = attend_self(q, k, v, ck, cv, plan.pos_dev, 0.125, workspace=plan.ws_self)
+                return F.linear(o.view(R, D), *L["out"])
+            return fn
+
+        def cross_attention(L, kv):
+            kx, vx = (kv[:, :, j * D:(j + 1) * D].view(B, P, H, 64).transpose(1, 2) for j in range(2))  # views, in place
+
+            def fn(y):
+                q = F.linear(y, *L["q_x"])
+                if G == 1:
+                    o = one(q.view(R, H, 64), kx, vx, 0.125, workspace=plan.ws_cross)
+                else:
+                    o = grouped(q.view(B, G, H, 64), kx, vx, 0.125, workspace=plan.ws_cross)
+                return F.linear(o.view(R, D), *L["out_x"])
+            return fn
+
+        return [s for L, kv, ck, cv in zip(self.layers, plan.cross, plan.self_k, plan.self_v)
+                for s in ((L["ln1"], self_attention(L, ck, cv)), (L["ln2"], cross_attention(L, kv)), (L["ln3"], _mlp(L)))]
 
     def _stages(self, st: DecoderState) -> list:
         """The three stages of every layer on the state's tensors and route, at the position the
@@ -643,7 +829,8 @@ class WhisperDecoder:
         beams are identical during the prompt, so the B chunks are computed through the caches'
         [::G] rows, which are then copied to the chunk's other G - 1 beams.  The GEMMs run at
         another row count than step's, so the logits agree with n steps to rounding, not bit for
-        bit.  Runs on the current stream."""
+        bit.  On a state from `start(graph=True)` prefill runs directly, as on any other, and the
+        plan's device position is then set to the new state.pos.  Runs on the current stream."""
         t = tokens if torch.is_tensor(tokens) else torch.as_tensor(tokens)
         if t.dim() != 2 or int(t.shape[1]) < 1:
             raise ValueError(f"WhisperDecoder.prefill: tokens must be [B, n] with n >= 1, got {tuple(t.shape)}")
@@ -705,6 +892,8 @@ class WhisperDecoder:
                     rows = cache.view(B, G, H, self.max_target_positions, 64)[:, :, :, :n]
                     rows[:, 1:].copy_(rows[:, :1].expand(B, G - 1, H, n, 64))
             st.pos += n
+            if st.graph is not None:  # the device position follows the host mirror
+                st.graph.pos_dev.fill_(st.pos)
             if all_positions:
                 return lg.view(B, n, self.V)
             return lg.repeat_interleave(G, 0) if G > 1 else lg
@@ -732,13 +921,13 @@ class WhisperDecoder:
 
     @torch.inference_mode()
     def logits(self, encoder_states: torch.Tensor, tokens, kernels: Optional[bool] = None,
-               prefill: bool = False) -> torch.Tensor:
+               prefill: bool = False, graph: bool = False) -> torch.Tensor:
         """Teacher-forced logits: tokens [B, n] -> [B, n, V], entry [:, i] the logits of the token
         after tokens[:, :i + 1]: n calls to step, or with `prefill` one call to
         prefill(all_positions=True).  `prefill` is off by default: its GEMMs run on B n rows and
         need not round as the stepwise ones do, and generate's tokens are pinned to the argmax of
-        this method's stepwise output exactly."""
-        st = self.start(encoder_states, kernels)
+        this method's stepwise output exactly.  `graph`: the steps are replays (start's `graph`)."""
+        st = self.start(encoder_states, kernels, graph=graph)
         t = tokens if torch.is_tensor(tokens) else torch.as_tensor(tokens)
         if t.dim() != 2:
             raise ValueError(f"WhisperDecoder.logits: tokens must be [B, n], got {tuple(t.shape)}")
@@ -762,7 +951,7 @@ class WhisperDecoder:
     @torch.inference_mode()
     def generate(self, encoder_states: torch.Tensor, prompt, eot: int, max_length: int = 448, suppress_tokens=(),
                  suppress_at_start=(), kernels: Optional[bool] = None, beam_size: int = 1, patience: float = 1.0,
-                 length_penalty: float = 1.0, prefill: bool = False) -> list:
+                 length_penalty: float = 1.0, prefill: bool = False, graph: bool = False, sync_every: int = 8) -> list:
         """Greedy decoding (asr.py:53-62 at beam_size 1, temperature 0): `prompt` (a list of ids,
         the same for every row) is fed one id per step; then every step takes the argmax of the
         logits with `suppress_tokens` at -inf, and at the first generated position also
@@ -774,10 +963,19 @@ class WhisperDecoder:
         every row (`patience` and `length_penalty` are beam_search's; greedy decoding ignores them).
         `prefill`: the prompt goes through one call to prefill instead of one step per id.  Off by
         default: prefill's GEMMs run at another row count and need not round as the stepwise ones
-        do, so the default keeps the tokens it gives today, bit for bit."""
+        do, so the default keeps the tokens it gives today, bit for bit.  `graph` (HIP route only):
+        every step is a replay of start's captured graph; the prompt goes through replays too, or
+        through an ordinary prefill.  The first selection runs as above; from then on the masking,
+        the argmax, the `done` update, the write of the ids into the step's token buffer and their
+        recording run on the device in a second small graph of the plan, and the host asks whether
+        every row is done only every `sync_every` generated steps (and never replays at a position
+        >= min(max_length, max_target_positions)).  Steps taken after every row finished feed
+        `eot` and are discarded, so the result equals graph=False token for token."""
+        if int(sync_every) < 1:
+            raise ValueError(f"WhisperDecoder.generate: sync_every must be at least 1, got {sync_every}")
         if int(beam_size) != 1:
             hyps = self.beam_search(encoder_states, prompt, eot, beam_size, patience, length_penalty, max_length,
-                                    suppress_tokens, suppress_at_start, kernels, prefill)
+                                    suppress_tokens, suppress_at_start, kernels, prefill, graph)
             return [h[0].ids if h else [] for h in hyps]
         prompt = [int(t) for t in prompt]
         eot = int(eot)
@@ -786,7 +984,7 @@ class WhisperDecoder:
         if not 0 <= eot < self.V:
             raise ValueError(f"WhisperDecoder.generate: eot {eot} is outside the vocabulary of {self.V}")
         always, first = self._id_list(suppress_tokens, "suppress_tokens"), self._id_list(suppress_at_start, "suppress_at_start")
-        st = self.start(encoder_states, kernels)
+        st = self.start(encoder_states, kernels, graph=graph)
         B = st.B
         ptok = self._tokens(torch.tensor(prompt).unsqueeze(0).expand(B, -1), (B, len(prompt)), "generate")
         limit = min(int(max_length), self.max_target_positions)
@@ -809,11 +1007,66 @@ class WhisperDecoder:
             done = done | (nxt == eot)
             if len(prompt) + len(steps) >= limit or bool(done.all()):
                 break
+            if st.graph is not None:
+                steps = self._generate_on_device(st, nxt, done, always, eot, limit - len(prompt), int(sync_every))
+                break
             lg = self._step(st, nxt)
         out = []
         for row in torch.stack(steps, 1).cpu().tolist():
             out.append(row[:row.index(eot)] if eot in row else row)
         return out
+
+    def _select_body(self, plan: _GraphPlan) -> None:
+        """generate's selection on the plan's tensors: the logits buffer masked by `suppress`, the
+        argmax (`eot` for the rows that are done), `done`, the ids into the token buffer and into
+        row `count` of the record, count += 1."""
+        plan.logits.masked_fill_(plan.suppress, float("-inf"))
+        nxt = torch.where(plan.done, plan.eot, plan.logits.argmax(-1))
+        plan.done.logical_or_(nxt == plan.eot)
+        plan.tok.copy_(nxt)
+        plan.record.index_copy_(0, plan.count, nxt.unsqueeze(0))
+        plan.count.add_(1)
+
+    def _generate_on_device(self, st: DecoderState, nxt: torch.Tensor, done: torch.Tensor, always, eot: int,
+                            budget: int, sync_every: int) -> list:
+        """generate's loop after the first selection (ids `nxt`, `done`; at least one row is live and
+        budget >= 2 ids may be generated in all): per step one replay of the step graph and one of
+        the selection graph, the completion asked of the device every `sync_every` generated steps.
+        Returns the ids of every step, the first included, as generate's `steps`."""
+        plan = st.graph
+        with self._ctx():
+            if plan.select is None:
+                dev, R = self.device, st.rows
+                plan.suppress = torch.zeros(self.V, dtype=torch.bool, device=dev)
+                plan.eot = torch.zeros(1, dtype=torch.int64, device=dev)
+                plan.done = torch.zeros(R, dtype=torch.bool, device=dev)
+                plan.count = torch.zeros(1, dtype=torch.int64, device=dev)
+                plan.record = torch.zeros((self.max_target_positions, R), dtype=torch.int64, device=dev)
+            plan.suppress.zero_()
+            if always is not None:
+                plan.suppress.index_fill_(0, always, True)
+            plan.eot.fill_(eot)
+            plan.done.copy_(done)
+            plan.tok.copy_(nxt)
+            plan.record[0].copy_(nxt)
+            plan.count.fill_(1)
+            n = 1
+            while n < budget:
+                self._graph_step(st, None)  # at position len(prompt) + n - 1 <= limit - 2
+                if plan.select is None:  # once per plan; the warm-up's effects on the state are undone
+                    keep = [t.clone() for t in (plan.done, plan.count, plan.tok)]
+                    self._warm_up(self.device, lambda: self._select_body(plan))
+                    for t, k in zip((plan.done, plan.count, plan.tok), keep):
+                        t.copy_(k)
+                    g = torch.cuda.CUDAGraph()
+                    with self._capturing(g):
+                        self._select_body(plan)
+                    plan.select = g
+                plan.select.replay()
+                n += 1
+                if n % sync_every == 0 and n < budget and bool(plan.done.all()):
+                    break
+            return list(plan.record[:n].unbind(0))
 
     def _select(self, lg: torch.Tensor, cum: torch.Tensor, G: int, kernels: bool):
         """wx_beam_topk's definition: per chunk the 2G best of cum[r] + log_softmax(lg[r])[t] as
@@ -834,7 +1087,7 @@ class WhisperDecoder:
     @torch.inference_mode()
     def beam_search(self, encoder_states: torch.Tensor, prompt, eot: int, beam_size: int = 5, patience: float = 1.0,
                     length_penalty: float = 1.0, max_length: int = 448, suppress_tokens=(), suppress_at_start=(),
-                    kernels: Optional[bool] = None, prefill: bool = False) -> list:
+                    kernels: Optional[bool] = None, prefill: bool = False, graph: bool = False) -> list:
         """Beam search (asr.py:301-304: the reference's default is beam_size 5, patience 1,
         length_penalty 1).  The structure is that of OpenAI's BeamSearchDecoder and
         MaximumLikelihoodRanker; this docstring is the specification.
@@ -857,7 +1110,9 @@ class WhisperDecoder:
         caches follow the beams by `reorder`; the 2G scores and indices of every chunk are the one
         host synchronisation of a step.  `prefill`: the prompt goes through one call to prefill on
         the B chunks (a chunk's beams are identical during the prompt) instead of one step per id
-        on B G rows; off by default, as in generate."""
+        on B G rows; off by default, as in generate.  `graph`: the step on the B G rows is a
+        replay of start's captured graph (HIP route only); the top-k, the host walk and `reorder`
+        are unchanged, and so are the hypotheses."""
         prompt = [int(t) for t in prompt]
         eot, G = int(eot), int(beam_size)
         if not prompt:
@@ -872,7 +1127,7 @@ class WhisperDecoder:
             raise ValueError(f"WhisperDecoder.beam_search: a vocabulary of {self.V} is smaller than 2 x beam_size")
         always, first = self._id_list(suppress_tokens, "suppress_tokens"), self._id_list(suppress_at_start, "suppress_at_start")
         max_finished = max(1, round(G * float(patience)))
-        st = self.start(encoder_states, kernels, beams=G)
+        st = self.start(encoder_states, kernels, beams=G, graph=graph)
         B, R, V = st.B, st.rows, self.V
         limit = min(int(max_length), self.max_target_positions)
         if B == 0 or len(prompt) >= limit:
