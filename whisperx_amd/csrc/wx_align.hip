@@ -247,9 +247,11 @@ __global__ __launch_bounds__(kWave) void column0_cumsum_kernel(const float* __re
         const int64_t t = t0 + (l & (kChunk - 1));
         const float e = t < T ? em[t * V] : 0.0f;
         const double a = col0_chunk(acc, e);
-        if (l < kChunk) S[t0 + l] = a;  // S(t0 + l), t0 + l < T
+        // S(t0 + l) for the chunk's rows that exist: the last chunk may be partial, and its lanes
+        // at and past T hold sums the header does not promise room for
+        if (l < kChunk && t0 + l < T) S[t0 + l] = a;
     }
-    if (l == 0) S[T] = acc;
+    if (l == 0) S[T] = acc;  // S(T): the sum over every row (the rows past T entered as 0)
 }
 }  // namespace wx
 
