@@ -46,6 +46,9 @@
  *                        prefix (the prompt of a batch in one forward: n queries per sequence and
  *                        head against the cache under a causal mask, and against the
  *                        cross-attention keys / values)
+ *   wx_sample_token   <- whisperx/asr.py:305-312  temperatures, log_prob_threshold (the selection
+ *                        of one greedy or sampled step with the token's log-probability: the
+ *                        passes of the temperature fallback)
  *
  * Conventions
  *   - All data pointers are DEVICE pointers (allocated by the caller; the library never
@@ -706,6 +709,45 @@ int wx_prefill_attention_h16(const void* q, const void* k, const void* v, void* 
 size_t wx_beam_topk_workspace_bytes(int32_t B, int32_t G, int32_t V);
 int wx_beam_topk(const float* logits, int64_t row_stride, const float* cum, int32_t B, int32_t G, int32_t V,
                  float* scores, int32_t* index, void* workspace, size_t workspace_bytes, void* stream);
+
+/* One greedy or sampled selection step (WhisperDecoder.sample, the passes of decode_with_fallback):
+ * R rows of V fp32 logits at logits + r row_stride (read, never written; nothing at columns >= V is
+ * read; no alignment is asked of row_stride).  For row r, with step = *step read on the device (so a
+ * captured launch draws a new stream at every replay):
+ *     m_t = -inf where suppress[t] != 0 (suppress may be NULL: no mask), else the logit; a logit of
+ *           -inf is an ordinary input.
+ *     done[r] != 0 on entry: token[r] = eot, logprob[r] = 0, sum_logprob[r] and done[r] left alone.
+ *     every m_t = -inf: token[r] = eot, logprob[r] = 0, done[r] = 1, sum_logprob[r] left alone.
+ *     otherwise token[r] = argmax_t z_t, the lowest t on ties, with
+ *         temperature == 0:  z_t = m_t;
+ *         temperature > 0:   z_t = m_t / temperature + g_t (Gumbel-max: a draw from
+ *                            softmax(m / temperature)), g_t = -log(-log(u_t)),
+ *                            u_t = ((x_t >> 9) + 0.5) 2^-23 (exact in fp32, never 0 or 1),
+ *                            x_t = word (t & 3) of Philox4x32-10 with counter
+ *                            (t >> 2, r, low word of step, high word of step) and key
+ *                            (low word of seed, high word of seed);
+ *       all in fp32 (a correctly rounded division, logf, one addition);
+ *     logprob[r] = m_token - lse, lse = M + log(sum_t exp(m_t - M)), M = max_t m_t: the
+ *       log-probability at temperature 1 whatever the temperature is, in fp32, in a summation order
+ *       that depends on V alone (slices of WX_SAMPLE_TOKEN_SLICE columns, each 4 x 1024; in a wave
+ *       lane i holds columns 256 e + 4 i + j of its 1024, e and j in 0..3: a lane's 16 columns in
+ *       ascending order, a butterfly over the wave, the 4 waves in order, then the slices 64 apart in
+ *       order and a butterfly);
+ *     sum_logprob[r] += logprob[r] (one fp32 addition; sum_logprob may be NULL);
+ *     done[r] |= (token[r] == eot).
+ * Row r's outputs are bit-identical whatever R is and whatever the other rows hold.  Two launches (a
+ * pass over the logits, one workgroup per slice and row; a merge, one wave per row), no atomics.
+ *   workspace: wx_sample_token_workspace_bytes(R, V) bytes (16-byte aligned).
+ * R < 0, V < 1 or V > 2^24, row_stride < V, a negative or non-finite temperature, eot outside
+ * [0, V): WX_E_INVALID; then R == 0: WX_OK; a null pointer (suppress and sum_logprob excepted), a
+ * misaligned workspace, R above 65535 (a grid dimension): WX_E_INVALID; a short workspace:
+ * WX_E_WORKSPACE; all before anything is enqueued. */
+#define WX_SAMPLE_TOKEN_SLICE 4096
+size_t wx_sample_token_workspace_bytes(int32_t R, int32_t V);
+int wx_sample_token(const float* logits, int64_t row_stride, int32_t R, int32_t V, const uint8_t* suppress,
+                    float temperature, uint64_t seed, const int64_t* step, int64_t eot, uint8_t* done,
+                    int64_t* token, float* logprob, float* sum_logprob, void* workspace, size_t workspace_bytes,
+                    void* stream);
 
 #ifdef __cplusplus
 }

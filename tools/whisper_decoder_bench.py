@@ -62,6 +62,13 @@ positions, 1500 encoder positions:
     L = 224 on 16 rows: wx_decode_self_attention_* against the two cache copies and
     wx_decode_attention_* on the same q/k/v GEMM output.
 
+(g) --arms sample (its own record, profiles/whisper_sample_<host>.json): sampling and the selection
+    kernel.  The selection launch alone, wx_sample_token on [16, 51865] and [80, 51865] logits at
+    temperature 0 and 0.6 with one suppressed id, against the torch chain it replaces (masked_fill,
+    log_softmax, argmax or torch.multinomial on softmax(l / T), gather); then, fp32 and float16 in
+    the same run, `sample` of 64 tokens x 16 chunks x best_of 5 at temperature 0.6 against
+    `beam_search` at --beams and greedy `generate`, each direct and with graph=True.
+
 Prints one JSON line; --out writes it to a file (profiles/whisper_decoder_<host>.json).
 """
 from __future__ import annotations
@@ -730,6 +737,91 @@ def graph_arm(name, g, args, torch, _lib, dev):
     return r
 
 
+def sample_arm(name, g, args, torch, _lib, dev):
+    """(g) for one geometry: the selection launch against the torch chain, then sample against
+    beam_search and generate, direct and graph, fp32 and float16."""
+    from transformers import WhisperConfig, WhisperForConditionalGeneration
+
+    from whisperx_amd import WhisperDecoder
+
+    D, G, H = g["D"], args.beams, g["D"] // 64
+    sync = torch.cuda.synchronize
+    eot = V - 1
+    r = {"shape": {**g, "heads": H, "vocab": V, "max_target_positions": T, "encoder_positions": P}, "beams": G,
+         "best_of": 5, "temperature": 0.6, "selection": []}
+    mask = torch.zeros(V, dtype=torch.bool, device=dev)
+    mask[eot] = True
+    ninf = float("-inf")
+    for R in (CHUNKS, CHUNKS * 5):
+        for temp in (0.0, 0.6):
+            ring = [3 * torch.randn((R, V), device=dev) for _ in range(8)]
+            done = torch.zeros(R, dtype=torch.bool, device=dev)
+            sums = torch.zeros(R, device=dev)
+            token, logprob = torch.empty(R, dtype=torch.int64, device=dev), torch.empty(R, device=dev)
+            step = torch.zeros(1, dtype=torch.int64, device=dev)
+            ws = _lib.sample_token_workspace(R, V, dev)
+
+            def kernel(i):
+                return _lib.sample_token(ring[i % 8], step, eot, done, temp, 1, mask, sums, token=token, logprob=logprob,
+                                         workspace=ws)
+
+            def chain(i):
+                m = ring[i % 8].masked_fill(mask, ninf)
+                lp = torch.log_softmax(m, -1)
+                tok = m.argmax(-1) if temp == 0 else torch.multinomial(torch.softmax(m / temp, -1), 1)[:, 0]
+                return tok, lp.gather(1, tok[:, None])[:, 0]
+
+            with torch.inference_mode():
+                row = {"rows": R, "vocab": V, "temperature": temp, "logit_bytes": 4 * R * V}
+                if temp == 0:  # (before the timed launches write the kernel's output tensors again)
+                    a, b = kernel(0), chain(0)
+                    row["tokens_equal"] = bool(torch.equal(a[0], b[0]))
+                    row["max_abs_diff_logprob"] = float((a[1] - b[1]).abs().max())
+                row["wx_sample_token"] = event_timed(kernel, args.repeat, args.warmup, args.steps, torch)
+                row["torch_chain"] = event_timed(chain, args.repeat, args.warmup, args.steps, torch)
+            row["wx_sample_token"]["logit_bytes_per_s"] = 4 * R * V / row["wx_sample_token"]["median_s"]
+            row["wx_sample_token"]["share_of_hbm_peak"] = row["wx_sample_token"]["logit_bytes_per_s"] / HBM_PEAK_BYTES_PER_S
+            row["kernel_vs_chain"] = beats(row["wx_sample_token"], row["torch_chain"])
+            r["selection"].append(row)
+            del ring
+            torch.cuda.empty_cache()
+    print(f"{name}: selection timed", file=sys.stderr, flush=True)
+    cfg = WhisperConfig(d_model=D, encoder_layers=1, encoder_attention_heads=1, encoder_ffn_dim=64, num_mel_bins=80,
+                        max_source_positions=P, decoder_layers=g["layers"], decoder_attention_heads=H,
+                        decoder_ffn_dim=4 * D, vocab_size=V, max_target_positions=T, pad_token_id=0, bos_token_id=1,
+                        eos_token_id=2, decoder_start_token_id=1)
+    hf = WhisperForConditionalGeneration(cfg).eval().model.decoder
+    for p in hf.parameters():
+        p.requires_grad_(False)
+    enc = torch.randn((CHUNKS, P, D), device=dev)
+    prompt = PROMPT + [50363]
+    kw = dict(max_length=len(prompt) + N_TOKENS, suppress_tokens=[eot])
+    for dt in (torch.float32, torch.float16):
+        label = str(dt).replace("torch.", "")
+        dec = WhisperDecoder(hf, device=dev, dtype=dt)
+        e = {}
+        for what, call in (("sample_best_of_5", lambda gr: dec.sample(enc, prompt, eot, temperature=0.6, best_of=5, seed=3, graph=gr, **kw)),
+                           ("beam_search", lambda gr: dec.beam_search(enc, prompt, eot, beam_size=G, graph=gr, **kw)),
+                           ("generate", lambda gr: dec.generate(enc, prompt, eot, graph=gr, **kw))):
+            a, b = call(True), call(False)
+            row = {"chunks": CHUNKS, "generated_tokens": N_TOKENS, "graph_equals_direct": a == b,
+                   "graph": timed(lambda: call(True), args.repeat, args.warmup, sync),
+                   "direct": timed(lambda: call(False), args.repeat, args.warmup, sync)}
+            row["graph_vs_direct"] = beats(row["graph"], row["direct"])
+            e[what] = row
+            print(f"{name} {label}: {what} timed", file=sys.stderr, flush=True)
+        for route in ("graph", "direct"):
+            e[f"sample_vs_beam_search_{route}"] = beats(e["sample_best_of_5"][route], e["beam_search"][route])
+            e[f"sample_vs_generate_{route}"] = beats(e["sample_best_of_5"][route], e["generate"][route])
+        e["graph_captures"] = dec.graph_captures
+        r[label] = e
+        dec.release_graphs()
+        del dec
+        torch.cuda.empty_cache()
+    del hf, enc
+    return r
+
+
 def step_once(dec, enc, tok, torch):
     """The logits of a direct state's step at STEP_POS after STEP_POS steps on `tok`."""
     st = dec.start(enc)
@@ -742,8 +834,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", default="float32", choices=["float32", "float16", "bfloat16"],
                     help="float16 / bfloat16: (d), the half route's record (profiles/whisper_decoder_half*_<host>.json)")
-    ap.add_argument("--arms", default="decoder", choices=["decoder", "beam", "prefill", "graph"],
-                    help="(a) and (b), (c), (e), or (f)")
+    ap.add_argument("--arms", default="decoder", choices=["decoder", "beam", "prefill", "graph", "sample"],
+                    help="(a) and (b), (c), (e), (f) or (g)")
     ap.add_argument("--beams", type=int, default=5)
     ap.add_argument("--geometries", default="base,large-v2")
     ap.add_argument("--repeat", type=int, default=5)
@@ -779,6 +871,12 @@ def main():
         for name in args.geometries.split(","):
             torch.manual_seed(args.seed)
             result["geometries"][name] = graph_arm(name, GEOMETRIES[name], args, torch, _lib, dev)
+        args.geometries = ""
+    if args.arms == "sample":
+        result["dtype"] = ["float32", "float16"]
+        for name in args.geometries.split(","):
+            torch.manual_seed(args.seed)
+            result["geometries"][name] = sample_arm(name, GEOMETRIES[name], args, torch, _lib, dev)
         args.geometries = ""
     eot = V - 1  # suppressed: both greedy loops run their full length
     if args.dtype != "float32":

@@ -44,7 +44,7 @@ from .audio import (  # noqa: F401
 from .vad import Binarize, merge_chunks  # noqa: F401
 from .diarize import assign_word_speakers, assign_word_speakers_batch  # noqa: F401
 from .writers import get_writer, format_timestamp  # noqa: F401
-from .whisper import Hypothesis, WhisperDecoder, WhisperEncoder, load_whisper_decoder, load_whisper_encoder  # noqa: F401
+from .whisper import DecodingResult, Hypothesis, WhisperDecoder, WhisperEncoder, load_whisper_decoder, load_whisper_encoder  # noqa: F401
 from .integration import install  # noqa: F401
 
 __version__ = "0.1.0"

@@ -27,7 +27,8 @@ SRC_PATHS = [SRC_PATH, os.path.join(_HERE, "csrc", "wx_binarize.hip"), os.path.j
              os.path.join(_HERE, "csrc", "wx_vad.hip"), os.path.join(_HERE, "csrc", "wx_diarize.hip"),
              os.path.join(_HERE, "csrc", "wx_mel.hip"), os.path.join(_HERE, "csrc", "wx_whisper.hip"),
              os.path.join(_HERE, "csrc", "wx_decode.hip"), os.path.join(_HERE, "csrc", "wx_beam.hip"),
-             os.path.join(_HERE, "csrc", "wx_attention_h16.hip"), os.path.join(_HERE, "csrc", "wx_prefill.hip")]
+             os.path.join(_HERE, "csrc", "wx_attention_h16.hip"), os.path.join(_HERE, "csrc", "wx_prefill.hip"),
+             os.path.join(_HERE, "csrc", "wx_sample.hip")]
 INST_PATH = os.path.join(_HERE, "csrc", "wx_align_inst.hip")
 HDR_PATHS = sorted(glob.glob(os.path.join(_HERE, "csrc", "*.h"))) + [INST_PATH]  # (a new header: a rebuild)
 INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
@@ -135,6 +136,9 @@ SIGNATURES = {
                                                     _vp, _vp, _f32, _vp, _vp, _sz, _vp]),
     "wx_decode_self_attention_h16": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
                                                     _vp, _vp, _f32, _i32, _vp, _vp, _sz, _vp]),
+    "wx_sample_token_workspace_bytes": (_sz, [_i32, _i32]),
+    "wx_sample_token": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _f32, ctypes.c_uint64, _vp, _i64, _vp, _vp, _vp, _vp,
+                                       _vp, _sz, _vp]),
 }
 
 
@@ -808,6 +812,64 @@ def beam_topk(logits: torch.Tensor, cum: torch.Tensor, G: int):
         _check(lib.wx_beam_topk(_ptr(logits), int(logits.stride(0)) if B * G > 1 else V, _ptr(cum), B, G, V,
                                 _ptr(scores), _ptr(index), _ptr(ws), ws.numel(), ctypes.c_void_p(stream.cuda_stream)))
     return scores, index
+
+
+SAMPLE_TOKEN_SLICE = 4096  # WX_SAMPLE_TOKEN_SLICE: columns per workgroup of wx_sample_token's first pass
+
+
+def sample_token_workspace(R: int, V: int, device) -> torch.Tensor:
+    """A workspace of exactly wx_sample_token_workspace_bytes(R, V) bytes on `device` (a graph plan's own)."""
+    return torch.empty(max(load().wx_sample_token_workspace_bytes(int(R), int(V)), 1), dtype=torch.uint8, device=device)
+
+
+def sample_token(logits: torch.Tensor, step: torch.Tensor, eot: int, done: torch.Tensor, temperature: float = 0.0,
+                 seed: int = 0, suppress: Optional[torch.Tensor] = None, sum_logprob: Optional[torch.Tensor] = None,
+                 token: Optional[torch.Tensor] = None, logprob: Optional[torch.Tensor] = None,
+                 workspace: Optional[torch.Tensor] = None):
+    """wx_sample_token: logits [R, V] fp32 (any row stride >= V, columns contiguous; read only),
+    `step` an int64 device tensor whose first element is the step counter (read on the device),
+    `done` [R] bool or uint8 (in / out), `suppress` [V] bool or uint8 (nonzero: the id is masked) or
+    None, `sum_logprob` [R] fp32 (in / out) or None -> (token [R] int64, logprob [R] fp32): per row
+    the argmax (temperature 0) or the Gumbel-max sample at `temperature` keyed on (seed, row, step)
+    of the masked logits and its log-probability at temperature 1; a row that is done gets `eot`
+    and 0.  `token` / `logprob`: tensors to write into instead of fresh ones; `workspace`: a uint8
+    tensor of at least wx_sample_token_workspace_bytes(R, V) bytes instead of the stream's scratch.
+    On the current stream."""
+    lib = load()
+    if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_cuda:
+        raise WXError(f"sample_token: logits must be a float32 [R, V] device tensor, got {logits.dtype} "
+                      f"{tuple(logits.shape)}")
+    dev = logits.device
+    R, V = int(logits.shape[0]), int(logits.shape[1])
+    if V > 1 and logits.stride(1) != 1:
+        raise WXError("sample_token: the logits' columns must be contiguous")
+    if token is None:
+        token = torch.empty(R, dtype=torch.int64, device=dev)
+    if logprob is None:
+        logprob = torch.empty(R, dtype=torch.float32, device=dev)
+
+    def fits(t, n, dtypes):
+        return t.dtype in dtypes and tuple(t.shape) == (n,) and t.device == dev and t.is_contiguous()
+
+    if not fits(done, R, (torch.bool, torch.uint8)) or not fits(token, R, (torch.int64,)) \
+            or not fits(logprob, R, (torch.float32,)) \
+            or (sum_logprob is not None and not fits(sum_logprob, R, (torch.float32,))) \
+            or (suppress is not None and not fits(suppress, V, (torch.bool, torch.uint8))):
+        raise WXError("sample_token: done [R] bool / uint8, token [R] int64, logprob and sum_logprob [R] float32 and "
+                      "suppress [V] bool / uint8 must be contiguous tensors on the logits' device")
+    if step.dtype != torch.int64 or step.device != dev or step.numel() < 1 or not step.is_contiguous():
+        raise WXError("sample_token: step must be a contiguous int64 tensor on the logits' device")
+    if not 0 <= int(seed) < 1 << 64:
+        raise WXError(f"sample_token: seed {seed} is not an unsigned 64-bit integer")
+    wsb = lib.wx_sample_token_workspace_bytes(R, V)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        ws = workspace if workspace is not None else _scratch.get("sample_token", dev, wsb, stream)
+        _check(lib.wx_sample_token(_ptr(logits), int(logits.stride(0)) if R > 1 else V, R, V, _ptr(suppress),
+                                   float(temperature), int(seed), _ptr(step), int(eot), _ptr(done), _ptr(token),
+                                   _ptr(logprob), _ptr(sum_logprob), _ptr(ws), ws.numel(),
+                                   ctypes.c_void_p(stream.cuda_stream)))
+    return token, logprob
 
 
 def sincnet_stage(x_tm: torch.Tensor, do_abs: bool, gamma, beta, eps: float, slope: float = 0.01,

@@ -1,8 +1,9 @@
 """Small host utilities mirrored from whisperx/utils.py (LANGUAGES_WITHOUT_SPACES :127,
-interpolate_nans :433-437)."""
+interpolate_nans :433-437), and faster-whisper's compression ratio."""
 from __future__ import annotations
 
 import math
+import zlib
 
 LANGUAGES_WITHOUT_SPACES = ["ja", "zh"]
 
@@ -30,3 +31,11 @@ def interpolate_nans(x, method="nearest"):
 
 def isnan(v) -> bool:
     return isinstance(v, float) and math.isnan(v)
+
+
+def compression_ratio(text: str) -> float:
+    """The UTF-8 byte length of `text` over the length of its zlib compression (faster-whisper's
+    get_compression_ratio): repetitive text compresses well and scores high, which the temperature
+    fallback reads as a failed decode (compression_ratio_threshold 2.4, asr.py:306)."""
+    data = text.encode("utf-8")
+    return len(data) / len(zlib.compress(data))

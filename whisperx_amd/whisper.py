@@ -40,7 +40,16 @@ one K_x / V_x (wx_decode_attention_f32_grouped), and the 2G best continuations o
 from wx_beam_topk.  `prefill` runs n positions in one pass instead (the prompt of generate /
 beam_search / logits with prefill=True): the same layers on [B n, D] rows, with
 wx_prefill_attention_f32 for the n queries against the cache under a causal mask and against
-K_x / V_x.  Temperature fallback, timestamps and the tokenizer are not built.
+K_x / V_x.
+
+Sampling and the temperature fallback (asr.py:305-312: temperatures 0 .. 1, compression_ratio_threshold
+2.4, log_prob_threshold -1, no_speech_threshold 0.6): `sample` decodes best_of candidates per chunk
+as the rows of a `start(beams=best_of)` state, every selection one wx_sample_token launch (the mask,
+the argmax or the Gumbel-max draw from a counter-based generator keyed on (seed, row, step), the
+token's log-probability at temperature 1, the done / eot handling), and `decode_with_fallback` is
+faster-whisper's generate_with_fallback on a batch: the chunks that fail a threshold are decoded
+again at the next temperature.  Timestamps, the tokenizer, condition_on_previous_text,
+repetition_penalty / no_repeat_ngram_size and top-k / top-p truncation are not built.
 
 With `graph=True` (start, generate, beam_search, logits; off by default, HIP route only) a step is
 one replay of a captured graph: the self-attention is wx_decode_self_attention_f32 (_h16), which
@@ -79,9 +88,11 @@ import torch.nn.functional as F
 
 from . import _lib
 from .audio import log_mel_chunks
+from .utils import compression_ratio
 
 _LN_EPS = 1e-5
 _MAX_PLANS = 2  # graph plans a WhisperDecoder keeps (start(graph=True))
+_MAX_SELECT_GRAPHS = 8  # selection graphs (one per eot, temperature and seed) a plan keeps for sample
 _MAX_BEAMS = _lib.DECODE_MAX_GROUP  # beams per chunk: the group size of wx_decode_attention_f32_grouped / wx_beam_topk
 
 
@@ -448,6 +459,48 @@ class Hypothesis(NamedTuple):
     score: float
 
 
+class DecodingResult(NamedTuple):
+    """One chunk's result of WhisperDecoder.decode_with_fallback: the chosen attempt's generated ids
+    (no prompt, no eot), the sum of their log-probabilities (eot's included), that sum per scored
+    position, the temperature of the attempt, the chunk's no-speech probability (None when no
+    token was given), the compression ratio of its text (None without `text_of`), whether the
+    silence exception made it final, and how many temperatures the chunk was decoded at."""
+    ids: list
+    sum_logprob: float
+    avg_logprob: float
+    temperature: float
+    no_speech_prob: Optional[float]
+    compression_ratio: Optional[float]
+    is_silence: bool
+    attempts: int
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3",
+    SC'11) on numpy arrays: `counter` four broadcastable arrays of 32-bit words, `key` two words ->
+    the four output words as uint64 arrays below 2^32."""
+    lo32 = np.uint64(0xFFFFFFFF)
+    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) & lo32 for c in counter)
+    k0, k1 = (int(k) & 0xFFFFFFFF for k in key)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2  # (32 x 32 bits: no overflow)
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ np.uint64(k0), p1 & lo32, (p0 >> np.uint64(32)) ^ c3 ^ np.uint64(k1), p0 & lo32
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return c0, c1, c2, c3
+
+
+def gumbel_uniforms(seed: int, R: int, V: int, step: int) -> np.ndarray:
+    """wx_sample_token's uniforms u [R, V] fp64 for `seed` and `step` (include/wx_align.h):
+    u[r][t] = ((x >> 9) + 0.5) 2^-23, x = word t & 3 of the Philox block with counter
+    (t >> 2, r, low word of step, high word of step) and key (low, high word of seed)."""
+    seed, step = int(seed), int(step)
+    q = np.arange((V + 3) // 4, dtype=np.uint64)[None, :]
+    r = np.arange(R, dtype=np.uint64)[:, None]
+    words = philox4x32_10((q, r, step & 0xFFFFFFFF, step >> 32), (seed & 0xFFFFFFFF, seed >> 32))
+    x = np.stack(np.broadcast_arrays(*words), -1).reshape(R, -1)[:, :V]
+    return ((x >> np.uint64(9)).astype(np.float64) + 0.5) * 2.0 ** -23
+
+
 class DecoderState:
     """What `WhisperDecoder.start` returns and `step` advances: per layer the cross-attention keys
     and values (`cross`: [B, P, 2D], the k half then the v half of one GEMM), the self-attention
@@ -495,6 +548,25 @@ class _GraphPlan:
         self.owner = lambda: None
         self.select = None
         self.suppress = self.eot = self.done = self.count = self.record = None
+        self.sample = None  # _SampleTensors: what sample's device-side selection needs, made at its first use
+
+
+class _SampleTensors:
+    """What sample's selection graphs of a plan own, apart from generate's: `suppress` [V] bool,
+    `done` [rows] bool, `sums` and `logprob` [rows] fp32, `count` int64 [1] (generated steps so far:
+    wx_sample_token's step counter), `record` [max_target_positions, rows] int64, the kernel's
+    workspace `ws`, and `graphs`: the captured selection per (eot, temperature, seed)."""
+
+    def __init__(self, dec: "WhisperDecoder", R: int):
+        dev = dec.device
+        self.suppress = torch.zeros(dec.V, dtype=torch.bool, device=dev)
+        self.done = torch.zeros(R, dtype=torch.bool, device=dev)
+        self.sums = torch.zeros(R, dtype=torch.float32, device=dev)
+        self.logprob = torch.zeros(R, dtype=torch.float32, device=dev)
+        self.count = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.record = torch.zeros((dec.max_target_positions, R), dtype=torch.int64, device=dev)
+        self.ws = _lib.sample_token_workspace(R, dec.V, dev)
+        self.graphs = {}
 
 
 class WhisperDecoder:
@@ -836,13 +908,15 @@ class WhisperDecoder:
             raise ValueError(f"WhisperDecoder.prefill: tokens must be [B, n] with n >= 1, got {tuple(t.shape)}")
         return self._prefill(state, self._tokens(t, (state.B, int(t.shape[1])), "prefill"), bool(all_positions))
 
-    def _prefill(self, st: DecoderState, tok: torch.Tensor, all_positions: bool) -> torch.Tensor:
-        """prefill() on checked ids [B, n] (n >= 1) already on the device."""
+    def _prefill(self, st: DecoderState, tok: torch.Tensor, all_positions: bool, identical: bool = False) -> torch.Tensor:
+        """prefill() on checked ids [B, n] (n >= 1) already on the device.  `identical`: the caller
+        vouches that a chunk's beams hold the same rows below state.pos (a prompt fed in pieces), so
+        a state of G beams may be prefilled there too."""
         B, G, P, D, H, pos, n = st.B, st.G, st.P, self.D, self.H, st.pos, int(tok.shape[1])
         if pos + n > self.max_target_positions:
             raise ValueError(f"WhisperDecoder.prefill: positions {pos} .. {pos + n - 1} run past max_target_positions "
                              f"({self.max_target_positions})")
-        if G > 1 and pos != 0:
+        if G > 1 and pos != 0 and not identical:
             raise ValueError(f"WhisperDecoder.prefill: a state of {G} beams is prefilled at position 0 only (its beams "
                              f"differ from position {pos} on)")
         half = self.dtype != torch.float32
@@ -889,7 +963,7 @@ class WhisperDecoder:
                 lg = F.linear(y, self.embed)
             if G > 1:  # the chunk's rows to its other beams
                 for cache in (*st.self_k, *st.self_v):
-                    rows = cache.view(B, G, H, self.max_target_positions, 64)[:, :, :, :n]
+                    rows = cache.view(B, G, H, self.max_target_positions, 64)[:, :, :, pos:pos + n]
                     rows[:, 1:].copy_(rows[:, :1].expand(B, G - 1, H, n, 64))
             st.pos += n
             if st.graph is not None:  # the device position follows the host mirror
@@ -1113,6 +1187,39 @@ class WhisperDecoder:
         on B G rows; off by default, as in generate.  `graph`: the step on the B G rows is a
         replay of start's captured graph (HIP route only); the top-k, the host walk and `reorder`
         are unchanged, and so are the hypotheses."""
+        return self._beam_search(encoder_states, prompt, eot, beam_size, patience, length_penalty, max_length,
+                                 suppress_tokens, suppress_at_start, kernels, prefill, graph)[0]
+
+    def _feed_prompt(self, st: DecoderState, ptok: torch.Tensor, prefill: bool, probe=None):
+        """The prompt ptok [rows, n] (the same ids in every row) into a fresh state, one step per id
+        or by prefill -> (the logits after its last id [rows, V], probabilities [B] or None).
+        `probe` = (sot_index, no_speech_token): the second value is
+        softmax(logits after prompt[sot_index])[no_speech_token] over the whole vocabulary, per
+        chunk, read on the way; prefill then feeds the prompt in two pieces, around sot_index."""
+        n, G = int(ptok.shape[1]), st.G
+        cut = n if probe is None else int(probe[0]) + 1
+        prob = None
+
+        def read(lg):
+            return torch.softmax(lg[::G], -1)[:, int(probe[1])].clone()
+
+        if prefill:
+            lg = self._prefill(st, ptok[::G, :cut], False)
+            if probe is not None:
+                prob = read(lg)
+            if cut < n:
+                lg = self._prefill(st, ptok[::G, cut:], False, identical=True)
+        else:
+            for i in range(n):
+                lg = self._step(st, ptok[:, i])
+                if i + 1 == cut and probe is not None:
+                    prob = read(lg)
+        return lg, prob
+
+    def _beam_search(self, encoder_states, prompt, eot, beam_size, patience, length_penalty, max_length,
+                     suppress_tokens, suppress_at_start, kernels, prefill, graph, probe=None):
+        """beam_search -> (its result, per chunk the scored positions n of every hypothesis in the
+        same order, _feed_prompt's probabilities for `probe` or None)."""
         prompt = [int(t) for t in prompt]
         eot, G = int(eot), int(beam_size)
         if not prompt:
@@ -1131,13 +1238,9 @@ class WhisperDecoder:
         B, R, V = st.B, st.rows, self.V
         limit = min(int(max_length), self.max_target_positions)
         if B == 0 or len(prompt) >= limit:
-            return [[] for _ in range(B)]
+            return [[] for _ in range(B)], [[] for _ in range(B)], None
         ptok = self._tokens(torch.tensor(prompt).unsqueeze(0).expand(R, -1), (R, len(prompt)), "beam_search")
-        if prefill:
-            lg = self._prefill(st, ptok[::G], False)
-        else:
-            for i in range(len(prompt)):
-                lg = self._step(st, ptok[:, i])
+        lg, prob = self._feed_prompt(st, ptok, prefill, probe)
         ninf = float("-inf")
         sums = [[0.0] + [ninf] * (G - 1) for _ in range(B)]
         ids = [[[] for _ in range(G)] for _ in range(B)]
@@ -1179,7 +1282,7 @@ class WhisperDecoder:
             if parents != identity:
                 self.reorder(st, torch.tensor(parents, dtype=torch.int64))
             lg = self._step(st, torch.tensor(feed, dtype=torch.int64).to(self.device))
-        out = []
+        out, ns = [], []
         for b in range(B):
             hyps = list(finished[b])
             if len(hyps) < max_finished:  # not done: the live beams, already in order of their sums
@@ -1187,9 +1290,282 @@ class WhisperDecoder:
                     if len(hyps) >= G:
                         break
                     hyps.append((ids[b][g], sums[b][g], max(1, len(ids[b][g]))))
-            ranked = [Hypothesis(i, s, s / n ** float(length_penalty)) for i, s, n in hyps]
-            out.append(sorted(ranked, key=lambda h: -h.score))  # (stable: earlier-found first on ties)
-        return out
+            ranked = [(Hypothesis(i, s, s / n ** float(length_penalty)), n) for i, s, n in hyps]
+            ranked.sort(key=lambda h: -h[0].score)  # (stable: earlier-found first on ties)
+            out.append([h for h, _ in ranked])
+            ns.append([n for _, n in ranked])
+        return out, ns, prob
+
+    # ------------------------------------------------------------- sampling, temperature fallback
+    def _select_token(self, lg: torch.Tensor, mask, temperature: float, seed: int, step: int, done: torch.Tensor,
+                      sums: torch.Tensor, eot: int):
+        """wx_sample_token's definition (include/wx_align.h) in torch ops, for the host route: lg
+        [R, V] fp32 logits, mask [V] bool or None, done [R] bool and sums [R] fp32 updated in place
+        -> (token [R] int64, logprob [R] fp32).  z and the log-probability are evaluated in fp64 on
+        the fp32 logits and the log-probability rounded to fp32 once; the sum is an fp32 addition."""
+        R, V = int(lg.shape[0]), int(lg.shape[1])
+        m = lg.double()
+        if mask is not None:
+            m = m.masked_fill(mask, float("-inf"))
+        z = m
+        if temperature > 0:
+            u = torch.from_numpy(gumbel_uniforms(seed, R, V, step)).to(m.device)
+            z = m / float(np.float32(temperature)) - torch.log(-torch.log(u))  # (the kernel's argument is an fp32)
+        top = z.max(-1, keepdim=True).values
+        cols = torch.arange(V, device=m.device).expand(R, V)
+        tok = torch.where(z == top, cols, V).min(-1).values.clamp_(max=V - 1)  # the lowest t on ties
+        lp = (m.gather(1, tok[:, None])[:, 0] - torch.logsumexp(m, -1)).float()
+        live = ~done & (m.max(-1).values > float("-inf"))
+        tok = torch.where(live, tok, eot)
+        sums.add_(torch.where(live, lp, 0.0))
+        done.logical_or_(~live | (tok == eot))
+        return tok, torch.where(live, lp, 0.0)
+
+    @torch.inference_mode()
+    def sample(self, encoder_states: torch.Tensor, prompt, eot: int, temperature: float = 0.0, best_of: int = 1,
+               seed: int = 0, max_length: int = 448, suppress_tokens=(), suppress_at_start=(),
+               kernels: Optional[bool] = None, prefill: bool = False, graph: bool = False, sync_every: int = 8) -> list:
+        """Greedy decoding or sampling with the sequences' log-probabilities (faster-whisper's
+        `temperature` and `best_of`; one pass of decode_with_fallback).  Per chunk `best_of`
+        candidates are decoded side by side as the rows b best_of + g of a `start(beams=best_of)`
+        state: they share the chunk's cross-attention keys and values and never change rows, so no
+        `reorder` is needed.  The prompt, the masks (`suppress_tokens` always, `suppress_at_start`
+        at the first generated position) and the stopping rules are generate's.
+
+        Every generated step is one wx_sample_token launch on the step's logits (include/wx_align.h
+        states the definition; the host route evaluates the same definition in torch ops): at
+        temperature 0 the argmax, the lowest id on ties; above 0 the Gumbel-max draw from
+        softmax(logits / temperature) with the uniforms of Philox4x32-10 keyed on `seed` and
+        counted by (id, row, step), the step being the number of ids generated so far, so the same
+        seed gives the same draws on every route.  A token's log-probability is
+        log_softmax(masked logits)[token] at temperature 1 whatever the temperature is (OpenAI's
+        rule: the sum scores the model's distribution, not the tempered one), summed per row in
+        fp32, the `eot` that ends a row included.  `temperature` 0 requires `best_of` 1: the ids are
+        then generate's.
+
+        Returns per chunk `best_of` Hypothesis(ids, sum_logprob, score), best first: ids without
+        the prompt and without `eot`, score = sum_logprob / n with n the ids plus one for an `eot`,
+        at least 1 (beam_search's rule at length_penalty 1), the earlier row first on ties.
+        `graph` (HIP route only): after the first selection a step is one replay of the step graph
+        and one of a small selection graph of the plan (wx_sample_token reading the step counter
+        from device memory, the ids into the token buffer and the record), and the host asks
+        whether every row is done every `sync_every` generated steps; the result equals
+        graph=False exactly, ids and sums.  A selection graph is captured per (temperature, seed,
+        eot) of a plan and kept; `graph_captures` counts step graphs only."""
+        return self._sample(encoder_states, prompt, eot, temperature, best_of, seed, max_length, suppress_tokens,
+                            suppress_at_start, kernels, prefill, graph, sync_every)[0]
+
+    def _sample(self, encoder_states, prompt, eot, temperature, best_of, seed, max_length, suppress_tokens,
+                suppress_at_start, kernels, prefill, graph, sync_every, probe=None):
+        """sample -> (its result, per chunk the scored positions n of every hypothesis in the same
+        order, _feed_prompt's probabilities for `probe` or None)."""
+        prompt = [int(t) for t in prompt]
+        eot, G, seed, T = int(eot), int(best_of), int(seed), float(temperature)
+        if not prompt:
+            raise ValueError("WhisperDecoder.sample: the prompt is empty")
+        if not 0 <= eot < self.V:
+            raise ValueError(f"WhisperDecoder.sample: eot {eot} is outside the vocabulary of {self.V}")
+        if not 1 <= G <= _MAX_BEAMS:
+            raise ValueError(f"WhisperDecoder.sample: best_of must lie in 1..{_MAX_BEAMS}, got {best_of}")
+        if not (T >= 0 and T != float("inf")):
+            raise ValueError(f"WhisperDecoder.sample: temperature must be finite and not negative, got {temperature}")
+        if T == 0 and G != 1:
+            raise ValueError(f"WhisperDecoder.sample: temperature 0 draws nothing, so best_of must be 1, got {best_of}")
+        if not 0 <= seed < 1 << 64:
+            raise ValueError(f"WhisperDecoder.sample: seed must be an unsigned 64-bit integer, got {seed}")
+        if int(sync_every) < 1:
+            raise ValueError(f"WhisperDecoder.sample: sync_every must be at least 1, got {sync_every}")
+        always, first = self._id_list(suppress_tokens, "suppress_tokens"), self._id_list(suppress_at_start, "suppress_at_start")
+        st = self.start(encoder_states, kernels, beams=G, graph=graph)
+        B, R, dev = st.B, st.rows, self.device
+        limit = min(int(max_length), self.max_target_positions)
+        if B == 0 or len(prompt) >= limit:
+            return [[Hypothesis([], 0.0, 0.0) for _ in range(G)] for _ in range(B)], [[1] * G for _ in range(B)], None
+        ptok = self._tokens(torch.tensor(prompt).unsqueeze(0).expand(R, -1), (R, len(prompt)), "sample")
+        lg, prob = self._feed_prompt(st, ptok, prefill, probe)
+        with self._ctx():
+            mask = mask0 = None
+            if always is not None or first is not None:
+                mask0 = torch.zeros(self.V, dtype=torch.bool, device=dev)
+                if always is not None:
+                    mask = mask0.index_fill(0, always, True)
+                    mask0 = mask.clone()
+                if first is not None:
+                    mask0.index_fill_(0, first, True)
+            done = torch.zeros(R, dtype=torch.bool, device=dev)
+            sums = torch.zeros(R, dtype=torch.float32, device=dev)
+            counter = torch.arange(limit, dtype=torch.int64, device=dev)  # element n: the step counter of step n
+            steps = []
+            while True:
+                n = len(steps)
+                if st.kernels:
+                    nxt, _ = _lib.sample_token(lg, counter[n:], eot, done, T, seed, mask if n else mask0, sums)
+                else:
+                    nxt, _ = self._select_token(lg, mask if n else mask0, T, seed, n, done, sums, eot)
+                steps.append(nxt)
+                if len(prompt) + len(steps) >= limit or bool(done.all()):
+                    break
+                if st.graph is not None:
+                    steps, sums = self._sample_on_device(st, nxt, done, sums, mask, eot, T, seed, limit - len(prompt),
+                                                         int(sync_every))
+                    break
+                lg = self._step(st, nxt)
+            rows, totals = torch.stack(steps, 1).cpu().tolist(), sums.cpu().tolist()
+        out, ns = [], []
+        for b in range(B):
+            ranked = []
+            for row, total in zip(rows[b * G:(b + 1) * G], totals[b * G:(b + 1) * G]):
+                ids = row[:row.index(eot)] if eot in row else row
+                n = max(1, len(ids) + (eot in row))
+                ranked.append((Hypothesis(ids, total, total / n), n))
+            ranked.sort(key=lambda h: -h[0].score)  # (stable: the earlier row first on ties)
+            out.append([h for h, _ in ranked])
+            ns.append([n for _, n in ranked])
+        return out, ns, prob
+
+    def _sample_body(self, plan: _GraphPlan, eot: int, temperature: float, seed: int) -> None:
+        """sample's selection on the plan's tensors: wx_sample_token on the logits buffer with the
+        step counter `count` read on the device, the ids straight into the step's token buffer,
+        then into row `count` of the record, count += 1."""
+        sm = plan.sample
+        _lib.sample_token(plan.logits, sm.count, eot, sm.done, temperature, seed, sm.suppress, sm.sums, token=plan.tok,
+                          logprob=sm.logprob, workspace=sm.ws)
+        sm.record.index_copy_(0, sm.count, plan.tok.unsqueeze(0))
+        sm.count.add_(1)
+
+    def _sample_on_device(self, st: DecoderState, nxt: torch.Tensor, done: torch.Tensor, sums: torch.Tensor, mask,
+                          eot: int, temperature: float, seed: int, budget: int, sync_every: int):
+        """sample's loop after the first selection, as _generate_on_device is generate's: per step
+        one replay of the step graph and one of the selection graph captured for (eot, temperature,
+        seed), which are arguments of the launch and so part of the graph.  Returns (the ids of
+        every step, the first included; the rows' sums)."""
+        plan = st.graph
+        with self._ctx():
+            if plan.sample is None:
+                plan.sample = _SampleTensors(self, st.rows)
+            sm = plan.sample
+            if mask is None:
+                sm.suppress.zero_()
+            else:
+                sm.suppress.copy_(mask)
+            sm.done.copy_(done)
+            sm.sums.copy_(sums)
+            plan.tok.copy_(nxt)
+            sm.record[0].copy_(nxt)
+            sm.count.fill_(1)
+            key = (eot, temperature, seed)
+            n = 1
+            while n < budget:
+                self._graph_step(st, None)  # at position len(prompt) + n - 1 <= limit - 2
+                g = sm.graphs.get(key)
+                if g is None:  # once per plan and key; the warm-up's effects on the state are undone
+                    state = (sm.done, sm.sums, sm.count, plan.tok)
+                    keep = [t.clone() for t in state]
+                    self._warm_up(self.device, lambda: self._sample_body(plan, *key))
+                    for t, k in zip(state, keep):
+                        t.copy_(k)
+                    g = torch.cuda.CUDAGraph()
+                    with self._capturing(g):
+                        self._sample_body(plan, *key)
+                    if len(sm.graphs) >= _MAX_SELECT_GRAPHS:
+                        sm.graphs.clear()
+                    sm.graphs[key] = g
+                g.replay()
+                n += 1
+                if n % sync_every == 0 and n < budget and bool(sm.done.all()):
+                    break
+            return list(sm.record[:n].unbind(0)), sm.sums.clone()
+
+    @torch.inference_mode()
+    def decode_with_fallback(self, encoder_states: torch.Tensor, prompt, eot: int,
+                             temperatures=(0.0, 0.2, 0.4, 0.6, 0.8, 1.0), beam_size: int = 5, patience: float = 1.0,
+                             length_penalty: float = 1.0, best_of: int = 5, log_prob_threshold: Optional[float] = -1.0,
+                             no_speech_threshold: Optional[float] = 0.6, no_speech_token: Optional[int] = None,
+                             sot_index: int = 0, compression_ratio_threshold: Optional[float] = 2.4, text_of=None,
+                             seed: int = 0, max_length: int = 448, suppress_tokens=(), suppress_at_start=(),
+                             kernels: Optional[bool] = None, prefill: bool = False, graph: bool = False,
+                             sync_every: int = 8) -> list:
+        """Temperature fallback (asr.py:305-312: temperatures 0 .. 1, compression_ratio_threshold
+        2.4, log_prob_threshold -1, no_speech_threshold 0.6): faster-whisper's
+        generate_with_fallback on a batch of chunks; this docstring is the specification.
+
+        All chunks start pending.  For every temperature, in order, the pending chunks are decoded
+        as one batch (an index_select of `encoder_states`, in their order): at temperature 0 by
+        beam_search with `beam_size`, `patience` and `length_penalty` (by sample at temperature 0
+        when beam_size is 1), above 0 by sample(temperature, best_of); the chunk's attempt is the
+        best hypothesis.  The pass at index i of `temperatures` uses `seed` + i.  Per attempt:
+
+            avg_logprob        sum_logprob / n, n the scored positions (the ids, plus one for an
+                               `eot`; at least 1)
+            compression_ratio  utils.compression_ratio(text_of(ids)) when `text_of` (ids -> str: the
+                               tokenizer stays with the caller) is given, else None
+            needs another temperature   compression_ratio > compression_ratio_threshold, or
+                               avg_logprob < log_prob_threshold
+            is_silence         no_speech_prob > no_speech_threshold and avg_logprob <
+                               log_prob_threshold: the chunk is final whatever the line above says
+
+        A threshold of None switches its check off.  A chunk that needs no other temperature is
+        final with that attempt.  After the last temperature a chunk that is still pending takes
+        its attempt with the highest avg_logprob, the earliest on ties.  `no_speech_prob` is
+        softmax(logits after prompt[sot_index])[no_speech_token] over the whole vocabulary, read
+        during the first pass's prompt (with `prefill` the prompt is then fed in two pieces, around
+        sot_index); None when `no_speech_token` is None.  The remaining arguments are generate's.
+
+        Returns per chunk DecodingResult(ids, sum_logprob, avg_logprob, temperature,
+        no_speech_prob, compression_ratio, is_silence, attempts): the chosen attempt, the
+        temperature it was decoded at and the number of attempts the chunk took."""
+        temps = [float(t) for t in temperatures]
+        if not temps:
+            raise ValueError("WhisperDecoder.decode_with_fallback: temperatures is empty")
+        if any(not (t >= 0 and t != float("inf")) for t in temps):
+            raise ValueError(f"WhisperDecoder.decode_with_fallback: temperatures must be finite and not negative, got {temps}")
+        n_prompt = len(list(prompt))
+        if not 0 <= int(sot_index) < n_prompt:
+            raise ValueError(f"WhisperDecoder.decode_with_fallback: sot_index {sot_index} is outside the prompt of "
+                             f"{n_prompt} ids")
+        if no_speech_token is not None and not 0 <= int(no_speech_token) < self.V:
+            raise ValueError(f"WhisperDecoder.decode_with_fallback: no_speech_token {no_speech_token} is outside the "
+                             f"vocabulary of {self.V}")
+        x = encoder_states
+        if not torch.is_tensor(x) or x.dim() != 3:
+            raise ValueError("WhisperDecoder.decode_with_fallback: encoder_states must be a [B, P, D] tensor")
+        B = int(x.shape[0])
+        pending, tried = list(range(B)), [[] for _ in range(B)]
+        final, silence_prob = [None] * B, [None] * B
+        for i, T in enumerate(temps):
+            if not pending:
+                break
+            sub = x if len(pending) == B else x.index_select(0, torch.tensor(pending, dtype=torch.int64, device=x.device))
+            probe = (int(sot_index), int(no_speech_token)) if i == 0 and no_speech_token is not None else None
+            if T == 0 and int(beam_size) != 1:
+                hyps, ns, prob = self._beam_search(sub, prompt, eot, beam_size, patience, length_penalty, max_length,
+                                                   suppress_tokens, suppress_at_start, kernels, prefill, graph, probe)
+            else:
+                hyps, ns, prob = self._sample(sub, prompt, eot, T, 1 if T == 0 else best_of, int(seed) + i, max_length,
+                                              suppress_tokens, suppress_at_start, kernels, prefill, graph, sync_every, probe)
+            if prob is not None:
+                for b, p in zip(pending, prob.cpu().tolist()):
+                    silence_prob[b] = p
+            still = []
+            for j, b in enumerate(pending):
+                h, n = (hyps[j][0], ns[j][0]) if hyps[j] else (Hypothesis([], 0.0, 0.0), 1)
+                avg = h.sum_logprob / n
+                ratio = None if text_of is None else compression_ratio(text_of(h.ids))
+                low = log_prob_threshold is not None and avg < log_prob_threshold
+                again = low or (compression_ratio_threshold is not None and ratio is not None
+                                and ratio > compression_ratio_threshold)
+                silent = low and no_speech_threshold is not None and silence_prob[b] is not None \
+                    and silence_prob[b] > no_speech_threshold
+                tried[b].append(DecodingResult(h.ids, h.sum_logprob, avg, T, silence_prob[b], ratio, silent, len(tried[b]) + 1))
+                if again and not silent:
+                    still.append(b)
+                else:
+                    final[b] = tried[b][-1]
+            pending = still
+        for b in pending:  # every temperature failed: the attempt with the highest avg_logprob, the earliest on ties
+            best = max(tried[b], key=lambda a: a.avg_logprob)
+            final[b] = best._replace(attempts=len(tried[b]))
+        return final
 
     @torch.inference_mode()
     def detect_language(self, encoder_states: torch.Tensor, sot: int, language_tokens,
