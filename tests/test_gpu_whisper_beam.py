@@ -7,12 +7,12 @@ WhisperDecoder.beam_search on the kernel route against the fp64 beam search of b
 import ctypes
 import math
 
-import numpy as np
 import pytest
 import torch
 
 import attention_probes as ap
 from beam_helpers import EOT, check_beam_search
+from selection_probes import _reference
 from whisper_decoder_helpers import GEOMETRIES, attention_inputs, case
 
 pytestmark = pytest.mark.gpu
@@ -172,23 +172,6 @@ def test_grouped_argument_checks():
 
 
 # ------------------------------------------------------------------------------ wx_beam_topk
-def _reference(x, cum, G, n):
-    """The definition in fp64: the first n candidates of every chunk as (scores [B, n], index [B, n])."""
-    x, cum = x.double(), cum.double()
-    R, V = x.shape
-    lse = torch.logsumexp(x, 1)
-    score = cum[:, None] + (x - lse[:, None])
-    score = torch.where((x == -math.inf) | (cum[:, None] == -math.inf), -math.inf, score)
-    s, xs = score.view(R // G, G * V).numpy(), x.view(R // G, G * V).numpy()
-    flat = np.arange(G * V)
-    sc, idx = [], []
-    for b in range(R // G):
-        order = np.lexsort((flat % V, -xs[b], flat // V, -s[b]))[:n]  # score desc, g, logit desc, t
-        sc.append(s[b][order])
-        idx.append(order)
-    return torch.from_numpy(np.stack(sc)), torch.from_numpy(np.stack(idx))
-
-
 def _padded(x, fill=math.nan):
     """x [R, V] on the device with a row stride > V and `fill` in the padding."""
     R, V = x.shape
