@@ -71,7 +71,13 @@ selection of beam search (wx_beam_topk on the fp32 logits).
 
 Without a GPU the same arithmetic runs in torch ops on the host (`F.conv1d`, `F.layer_norm`,
 `F.scaled_dot_product_attention`).  Both halves read their weights through one loader (`_Half`,
-`_Taker`) and run their layers as stages of one residual chain (`_chain`) on either route.
+`_Taker`) and run their layers as stages of one residual chain on either route (`_run_chain`:
+`_chain`, or `_chain_half` for float16 / bfloat16).  The decoder builds its stages in one place
+(`_layer_stages`; the direct step, the graph step and prefill supply what "attend" means) between one
+pair of ends (`_embed`, `_project`).  generate, beam_search and sample open alike (`_check_prompt`,
+`_open`, `_budget`, `_feed_prompt`) and close alike (`_cut`, `_rank`); generate and sample are one
+row-wise loop (`_decode_rows`) around their selection, which on a graph state goes on as one loop of
+replays (`_decode_on_device`) on one `_Selection` per plan.
 """
 from __future__ import annotations
 
@@ -92,7 +98,7 @@ from .utils import compression_ratio
 
 _LN_EPS = 1e-5
 _MAX_PLANS = 2  # graph plans a WhisperDecoder keeps (start(graph=True))
-_MAX_SELECT_GRAPHS = 8  # selection graphs (one per eot, temperature and seed) a plan keeps for sample
+_MAX_SELECT_GRAPHS = 8  # selection graphs a plan keeps (generate's one; sample's one per eot, temperature and seed)
 _MAX_BEAMS = _lib.DECODE_MAX_GROUP  # beams per chunk: the group size of wx_decode_attention_f32_grouped / wx_beam_topk
 
 
@@ -305,6 +311,14 @@ def _chain_half(h: torch.Tensor, stages: list, final, dtype: torch.dtype, kernel
     return _lib.add_layernorm(select(h), stages[-1][1](select(y)).float(), *final, _LN_EPS)
 
 
+def _run_chain(h: torch.Tensor, stages: list, final, dtype: torch.dtype, kernels: bool, select=None) -> torch.Tensor:
+    """The residual chain of a model of `dtype`, on the HIP route (`kernels`: the fused add-norm
+    kernels) or in torch ops: _chain for float32, _chain_half for float16 / bfloat16."""
+    if dtype != torch.float32:
+        return _chain_half(h, stages, final, dtype, kernels, select)
+    return _chain(h, stages, final, _lib.add_layernorm if kernels else None, select)
+
+
 _DTYPES = (torch.float32, torch.float16, torch.bfloat16)
 
 
@@ -425,9 +439,7 @@ class WhisperEncoder:
             return F.linear(attend(q, k, v), *L["out"])
 
         stages = [s for L in self.layers for s in ((L["ln1"], lambda y, L=L: attention(y, L)), (L["ln2"], _mlp(L)))]
-        if half:
-            return _chain_half(h, stages, self.ln_post, self.dtype, kernel).view(B, P, D)
-        return _chain(h, stages, self.ln_post, _lib.add_layernorm if kernel else None).view(B, P, D)
+        return _run_chain(h, stages, self.ln_post, self.dtype, kernel).view(B, P, D)
 
 
 def _load_state_dict(path: str, who: str) -> dict:
@@ -526,10 +538,8 @@ class _GraphPlan:
     (the state's `cross` and caches, `pos_dev` int32 [1], the token buffer `tok` [rows] int64, the
     logits buffer [rows, V] fp32, the attention workspaces), the stages bound to them, and the
     captured step graph (`graph`, None until the first step).  `owner`: a weak reference to the state
-    the plan is bound to; the plan is free again when that state is gone.  For greedy decoding
-    (G = 1) also what the device-side selection needs, and its small graph `select`: `suppress`
-    [V] bool (the ids at -inf), `eot` int64 [1], `done` [rows] bool, `count` int64 [1] (generated
-    steps so far) and `record` [max_target_positions, rows] int64 (the ids of every step)."""
+    the plan is bound to; the plan is free again when that state is gone.  `selection`: the
+    _Selection of generate's and sample's device-side loop, made at its first use."""
 
     def __init__(self, dec: "WhisperDecoder", B: int, G: int, P: int):
         dev, dt, R = dec.device, dec.dtype, B * G
@@ -546,27 +556,35 @@ class _GraphPlan:
         self.stages = None
         self.graph = None
         self.owner = lambda: None
-        self.select = None
-        self.suppress = self.eot = self.done = self.count = self.record = None
-        self.sample = None  # _SampleTensors: what sample's device-side selection needs, made at its first use
+        self.selection = None
 
 
-class _SampleTensors:
-    """What sample's selection graphs of a plan own, apart from generate's: `suppress` [V] bool,
-    `done` [rows] bool, `sums` and `logprob` [rows] fp32, `count` int64 [1] (generated steps so far:
-    wx_sample_token's step counter), `record` [max_target_positions, rows] int64, the kernel's
-    workspace `ws`, and `graphs`: the captured selection per (eot, temperature, seed)."""
+class _Selection:
+    """What the device-side selection of a plan owns, for generate and for sample: `suppress` [V]
+    bool (the ids at -inf), `done` [rows] bool, `count` int64 [1] (generated steps so far:
+    wx_sample_token's step counter), `record` [max_target_positions, rows] int64 (the ids of every
+    step), greedy's `eot` int64 [1], and `graphs`: the captured selections, greedy's one under
+    "greedy" and sample's under (eot, temperature, seed), which are arguments of its launch; at
+    most _MAX_SELECT_GRAPHS in all.  Sample's own `sums` and `logprob` [rows] fp32 and its kernel's
+    workspace `ws` are made by `for_sample` at sample's first use."""
 
     def __init__(self, dec: "WhisperDecoder", R: int):
         dev = dec.device
         self.suppress = torch.zeros(dec.V, dtype=torch.bool, device=dev)
+        self.eot = torch.zeros(1, dtype=torch.int64, device=dev)
         self.done = torch.zeros(R, dtype=torch.bool, device=dev)
-        self.sums = torch.zeros(R, dtype=torch.float32, device=dev)
-        self.logprob = torch.zeros(R, dtype=torch.float32, device=dev)
         self.count = torch.zeros(1, dtype=torch.int64, device=dev)
         self.record = torch.zeros((dec.max_target_positions, R), dtype=torch.int64, device=dev)
-        self.ws = _lib.sample_token_workspace(R, dec.V, dev)
         self.graphs = {}
+        self.sums = self.logprob = self.ws = None
+
+    def for_sample(self) -> "_Selection":
+        if self.ws is None:
+            R, V, dev = int(self.done.shape[0]), int(self.suppress.shape[0]), self.done.device
+            self.sums = torch.zeros(R, dtype=torch.float32, device=dev)
+            self.logprob = torch.zeros(R, dtype=torch.float32, device=dev)
+            self.ws = _lib.sample_token_workspace(R, V, dev)
+        return self
 
 
 class WhisperDecoder:
@@ -729,15 +747,20 @@ class WhisperDecoder:
         if st.stages is None:  # once per state: the step path only calls them
             st.stages = self._stages(weakref.proxy(st))  # (a proxy: the state owns its stages, not they it)
         with self._ctx():
-            if self.dtype != torch.float32:
-                h = F.embedding(tok, self.embed).float() + self.pos[st.pos]
-                y = _chain_half(h, st.stages, self.ln_f, self.dtype, st.kernels)
-                st.pos += 1
-                return F.linear(y.to(self.dtype), self.embed).float()
-            h = F.embedding(tok, self.embed) + self.pos[st.pos]
-            y = _chain(h, st.stages, self.ln_f, _lib.add_layernorm if st.kernels else None)
+            y = _run_chain(self._embed(tok, self.pos[st.pos]), st.stages, self.ln_f, self.dtype, st.kernels)
             st.pos += 1
-            return F.linear(y, self.embed)
+            return self._project(y)
+
+    def _embed(self, tok: torch.Tensor, pos_rows: torch.Tensor) -> torch.Tensor:
+        """Ids and the rows of the positional table at their positions -> the fp32 stream: the
+        embedding's rows (widened, on a float16 / bfloat16 decoder) + pos_rows."""
+        return F.embedding(tok, self.embed).float() + pos_rows
+
+    def _project(self, y: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The final norm's output -> the fp32 logits (into `out`, when given): the tied output
+        projection as a GEMM in the decoder's dtype, its result widened."""
+        lg = F.linear(y.to(self.dtype), self.embed)
+        return lg.float() if out is None else out.copy_(lg)
 
     def _graph_step(self, st: DecoderState, tok: Optional[torch.Tensor]) -> torch.Tensor:
         """_step on a graph state (the position already checked on the host mirror): the ids into
@@ -755,24 +778,8 @@ class WhisperDecoder:
     def _graph_body(self, plan: _GraphPlan) -> None:
         """One step on the plan's tensors at the position in plan.pos_dev, which it leaves as it
         is: _step's arithmetic, the position read on the device."""
-        half = self.dtype != torch.float32
-        e = F.embedding(plan.tok, self.embed)
-        h = (e.float() if half else e) + self.pos.index_select(0, plan.pos_dev)
-        if half:
-            y = _chain_half(h, plan.stages, self.ln_f, self.dtype, True)
-            plan.logits.copy_(F.linear(y.to(self.dtype), self.embed))
-        else:
-            plan.logits.copy_(F.linear(_chain(h, plan.stages, self.ln_f, _lib.add_layernorm), self.embed))
-
-    @staticmethod
-    def _warm_up(device, body) -> None:
-        """`body` once on a side stream, ordered after and before the current one: what torch asks
-        for before a capture (libraries initialised, kernels loaded)."""
-        cur, side = torch.cuda.current_stream(device), torch.cuda.Stream(device)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            body()
-        cur.wait_stream(side)
+        h = self._embed(plan.tok, self.pos.index_select(0, plan.pos_dev))
+        self._project(_run_chain(h, plan.stages, self.ln_f, self.dtype, True), out=plan.logits)
 
     @staticmethod
     @contextlib.contextmanager
@@ -791,97 +798,109 @@ class WhisperDecoder:
             if was_on:
                 gc.enable()
 
-    def _capture(self, plan: _GraphPlan) -> None:
-        """The plan's step graph: body, then pos_dev += 1, one linear chain on the capture stream."""
-        if plan.stages is None:  # (a proxy: the plan owns its stages, not they it, so it dies by reference count)
-            plan.stages = self._graph_stages(weakref.proxy(plan))
-        self._warm_up(self.device, lambda: (self._graph_body(plan), self._graph_body(plan)))
+    def _captured(self, body, warm=None, state=()):
+        """`body` as a captured graph, one linear chain on the capture stream.  `warm` (by default
+        `body`) runs once before on a side stream, ordered after and before the current one: what
+        torch asks for before a capture (libraries initialised, kernels loaded); its effects on
+        the tensors `state` are undone."""
+        keep = [t.clone() for t in state]
+        cur, side = torch.cuda.current_stream(self.device), torch.cuda.Stream(self.device)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            (warm or body)()
+        cur.wait_stream(side)
+        for t, k in zip(state, keep):
+            t.copy_(k)
         g = torch.cuda.CUDAGraph()
         with self._capturing(g):
-            self._graph_body(plan)
-            plan.pos_dev.add_(1)
-        plan.graph = g
+            body()
+        return g
+
+    def _capture(self, plan: _GraphPlan) -> None:
+        """The plan's step graph: body, then pos_dev += 1.  The warm-up is the body twice: without
+        the increment it only rewrites cache row `pos` with the same values."""
+        if plan.stages is None:  # (a proxy: the plan owns its stages, not they it, so it dies by reference count)
+            plan.stages = self._graph_stages(weakref.proxy(plan))
+        plan.graph = self._captured(lambda: (self._graph_body(plan), plan.pos_dev.add_(1)),
+                                    warm=lambda: (self._graph_body(plan), self._graph_body(plan)))
         self.graph_captures += 1
+
+    def _layer_stages(self, cross, self_k, self_v, B: int, P: int, attend_self, attend_cross) -> list:
+        """The three stages (ln, fn) of every layer on a state's or a plan's tensors, for _run_chain.
+        What "attend" means is the caller's: attend_self(q, k, v, ck, cv) on the [rows, H, 64] thirds
+        of the q/k/v GEMM's output and the layer's caches, attend_cross(q, kx, vx) on the q GEMM's
+        output [rows, D] and the layer's [B, H, P, 64] views of `cross`; both return [rows, D]."""
+        D, H = self.D, self.H
+
+        def self_attention(L, ck, cv):
+            def fn(y):
+                q, k, v = F.linear(y, *L["qkv"]).view(-1, 3, H, 64).unbind(1)  # one GEMM, [rows, 3D]
+                return F.linear(attend_self(q, k, v, ck, cv), *L["out"])
+            return fn
+
+        def cross_attention(L, kv):
+            kx, vx = (kv[:, :, j * D:(j + 1) * D].view(B, P, H, 64).transpose(1, 2) for j in range(2))  # views, in place
+            return lambda y: F.linear(attend_cross(F.linear(y, *L["q_x"]), kx, vx), *L["out_x"])
+
+        return [s for L, kv, ck, cv in zip(self.layers, cross, self_k, self_v)
+                for s in ((L["ln1"], self_attention(L, ck, cv)), (L["ln2"], cross_attention(L, kv)), (L["ln3"], _mlp(L)))]
+
+    def _cross_kernel(self, B: int, G: int, workspace: Optional[torch.Tensor] = None):
+        """_layer_stages' attend_cross of one position on the HIP route: wx_decode_attention_f32
+        (_h16) on the B rows, or its grouped form on a chunk's G beams and the chunk's one K / V."""
+        R, D, H = B * G, self.D, self.H
+        half = self.dtype != torch.float32
+        if G == 1:
+            one = _lib.decode_attention_h16 if half else _lib.decode_attention_f32
+            return lambda q, kx, vx: one(q.view(R, H, 64), kx, vx, 0.125, workspace=workspace).view(R, D)
+        grouped = _lib.decode_attention_h16_grouped if half else _lib.decode_attention_f32_grouped
+        return lambda q, kx, vx: grouped(q.view(B, G, H, 64), kx, vx, 0.125, workspace=workspace).view(R, D)
 
     def _graph_stages(self, plan: _GraphPlan) -> list:
         """_stages on a plan's tensors for the graph: the self-attention is one call of
-        wx_decode_self_attention_f32 (_h16) on the q/k/v GEMM output, which reads the position on
-        the device and appends the cache row itself; the cross-attention is _stages' (its L = P is
-        a constant).  Every call uses the plan's workspaces."""
+        wx_decode_self_attention_f32 (_h16), which reads the position on the device and appends the
+        cache row itself; the cross-attention is _stages' (its L = P is a constant).  Every call
+        uses the plan's workspaces."""
         B, G, P = plan.key
-        R, D, H = B * G, self.D, self.H
-        half = self.dtype != torch.float32
-        attend_self = _lib.decode_self_attention_h16 if half else _lib.decode_self_attention_f32
-        one = _lib.decode_attention_h16 if half else _lib.decode_attention_f32
-        grouped = _lib.decode_attention_h16_grouped if half else _lib.decode_attention_f32_grouped
+        R, D = B * G, self.D
+        fused = _lib.decode_self_attention_f32 if self.dtype == torch.float32 else _lib.decode_self_attention_h16
 
-        def self_attention(L, ck, cv):
-            def fn(y):
-                qkv = F.linear(y, *L["qkv"])  # [R, 3D]
-                q, k, v = (qkv[:, j * D:(j + 1) * D].view(R, H, 64) for j in range(3))
-                o = attend_self(q, k, v, ck, cv, plan.pos_dev, 0.125, workspace=plan.ws_self)
-                return F.linear(o.view(R, D), *L["out"])
-            return fn
+        def attend_self(q, k, v, ck, cv):
+            return fused(q, k, v, ck, cv, plan.pos_dev, 0.125, workspace=plan.ws_self).view(R, D)
 
-        def cross_attention(L, kv):
-            kx, vx = (kv[:, :, j * D:(j + 1) * D].view(B, P, H, 64).transpose(1, 2) for j in range(2))  # views, in place
-
-            def fn(y):
-                q = F.linear(y, *L["q_x"])
-                if G == 1:
-                    o = one(q.view(R, H, 64), kx, vx, 0.125, workspace=plan.ws_cross)
-                else:
-                    o = grouped(q.view(B, G, H, 64), kx, vx, 0.125, workspace=plan.ws_cross)
-                return F.linear(o.view(R, D), *L["out_x"])
-            return fn
-
-        return [s for L, kv, ck, cv in zip(self.layers, plan.cross, plan.self_k, plan.self_v)
-                for s in ((L["ln1"], self_attention(L, ck, cv)), (L["ln2"], cross_attention(L, kv)), (L["ln3"], _mlp(L)))]
+        return self._layer_stages(plan.cross, plan.self_k, plan.self_v, B, P, attend_self,
+                                  self._cross_kernel(B, G, plan.ws_cross))
 
     def _stages(self, st: DecoderState) -> list:
-        """The three stages of every layer on the state's tensors and route, at the position the
-        state is at when they are called: both attentions on wx_decode_attention_f32 or on
-        torch's; the first writes the cache rows.  A state of G > 1 beams runs the self-attention
-        over its R = B G rows and the cross-attention of a chunk's G beams on the chunk's one
-        K / V: wx_decode_attention_f32_grouped, or torch's on a view expanded over the beams.  A
-        float16 / bfloat16 decoder takes wx_decode_attention_h16 and its grouped form, or torch's
-        attention in that dtype, on the dtype tensors of the state."""
+        """_layer_stages on the state's tensors and route, at the position the state is at when they
+        are called: the self-attention writes the cache rows and runs over the R = B G rows, the
+        cross-attention of a chunk's G beams reads the chunk's one K / V; wx_decode_attention_f32
+        (_h16) and _cross_kernel, or torch's attention (on a view expanded over the beams) in the
+        decoder's dtype."""
         B, G, R, P, D, H = st.B, st.G, st.rows, st.P, self.D, self.H
         if st.kernels:
-            half = self.dtype != torch.float32
-            one = _lib.decode_attention_h16 if half else _lib.decode_attention_f32
-            grouped = _lib.decode_attention_h16_grouped if half else _lib.decode_attention_f32_grouped
+            one = _lib.decode_attention_f32 if self.dtype == torch.float32 else _lib.decode_attention_h16
+            attend_cross = self._cross_kernel(B, G)
 
-            def attend(q, k, v, n=None):
-                return one(q, k, v, 0.125, L=n).view(R, D)
-
-            def attend_beams(q, k, v):
-                return grouped(q.view(B, G, H, 64), k, v, 0.125).view(R, D)
+            def attend(q, ck, cv, n):
+                return one(q, ck, cv, 0.125, L=n).view(R, D)
         else:
-            def attend(q, k, v, n=None):
-                return F.scaled_dot_product_attention(q.unsqueeze(2), k[:, :, :n], v[:, :, :n], scale=0.125).reshape(R, D)
+            def attend(q, ck, cv, n):
+                return F.scaled_dot_product_attention(q.unsqueeze(2), ck[:, :, :n], cv[:, :, :n], scale=0.125).reshape(R, D)
 
-            def attend_beams(q, k, v):  # k / v [B, H, P, 64] -> [B, G, H, P, 64]: a view, stride 0 over the beams
-                k, v = (t.unsqueeze(1).expand(B, G, H, P, 64) for t in (k, v))
-                return F.scaled_dot_product_attention(q.view(B, G, H, 1, 64), k, v, scale=0.125).reshape(R, D)
-        attend_x = attend if G == 1 else attend_beams
+            def attend_cross(q, kx, vx):
+                if G == 1:
+                    return F.scaled_dot_product_attention(q.view(R, H, 1, 64), kx, vx, scale=0.125).reshape(R, D)
+                kx, vx = (t.unsqueeze(1).expand(B, G, H, P, 64) for t in (kx, vx))  # views, stride 0 over the beams
+                return F.scaled_dot_product_attention(q.view(B, G, H, 1, 64), kx, vx, scale=0.125).reshape(R, D)
 
-        def self_attention(L, ck, cv):
-            def fn(y):
-                pos = st.pos
-                qkv = F.linear(y, *L["qkv"])  # [R, 3D]
-                q, k, v = (qkv[:, j * D:(j + 1) * D].view(R, H, 64) for j in range(3))
-                ck[:, :, pos].copy_(k)
-                cv[:, :, pos].copy_(v)
-                return F.linear(attend(q, ck, cv, pos + 1), *L["out"])
-            return fn
+        def attend_self(q, k, v, ck, cv):
+            pos = st.pos
+            ck[:, :, pos].copy_(k)
+            cv[:, :, pos].copy_(v)
+            return attend(q, ck, cv, pos + 1)
 
-        def cross_attention(L, kv):
-            kx, vx = (kv[:, :, j * D:(j + 1) * D].view(B, P, H, 64).transpose(1, 2) for j in range(2))  # views, in place
-            return lambda y: F.linear(attend_x(F.linear(y, *L["q_x"]).view(R, H, 64), kx, vx), *L["out_x"])
-
-        return [s for L, kv, ck, cv in zip(self.layers, st.cross, st.self_k, st.self_v)
-                for s in ((L["ln1"], self_attention(L, ck, cv)), (L["ln2"], cross_attention(L, kv)), (L["ln3"], _mlp(L)))]
+        return self._layer_stages(st.cross, st.self_k, st.self_v, B, P, attend_self, attend_cross)
 
     @torch.inference_mode()
     def prefill(self, state: DecoderState, tokens, all_positions: bool = False) -> torch.Tensor:
@@ -933,34 +952,21 @@ class WhisperDecoder:
                 o = F.scaled_dot_product_attention(q, k[:, :, :Tk], v[:, :, :Tk], attn_mask=mask, scale=0.125)
                 return o.transpose(1, 2).reshape(B * n, D)
 
-        def self_attention(L, ck, cv):
+        def attend_self(q, k, v, ck, cv):
             ck, cv = ck[::G], cv[::G]  # one row per chunk: views, in place
+            q, k, v = (t.view(B, n, H, 64).transpose(1, 2) for t in (q, k, v))  # [B, H, n, 64] views
+            ck[:, :, pos:pos + n].copy_(k)
+            cv[:, :, pos:pos + n].copy_(v)
+            return attend(q, ck, cv, pos, pos + n)
 
-            def fn(y):
-                qkv = F.linear(y, *L["qkv"]).view(B, n, 3, H, 64)  # one GEMM on [B n, D]
-                q, k, v = (qkv[:, :, j].transpose(1, 2) for j in range(3))  # [B, H, n, 64] views
-                ck[:, :, pos:pos + n].copy_(k)
-                cv[:, :, pos:pos + n].copy_(v)
-                return F.linear(attend(q, ck, cv, pos, pos + n), *L["out"])
-            return fn
+        def attend_cross(q, kx, vx):
+            return attend(q.view(B, n, H, 64).transpose(1, 2), kx, vx)
 
-        def cross_attention(L, kv):
-            kx, vx = (kv[:, :, j * D:(j + 1) * D].view(B, P, H, 64).transpose(1, 2) for j in range(2))  # views, in place
-            return lambda y: F.linear(attend(F.linear(y, *L["q_x"]).view(B, n, H, 64).transpose(1, 2), kx, vx),
-                                      *L["out_x"])
-
-        stages = [s for L, kv, ck, cv in zip(self.layers, st.cross, st.self_k, st.self_v)
-                  for s in ((L["ln1"], self_attention(L, ck, cv)), (L["ln2"], cross_attention(L, kv)), (L["ln3"], _mlp(L)))]
+        stages = self._layer_stages(st.cross, st.self_k, st.self_v, B, P, attend_self, attend_cross)
         select = None if all_positions else (lambda t: t.view(B, n, t.shape[-1])[:, n - 1])
         with self._ctx():
-            e = F.embedding(tok, self.embed)
-            h = ((e.float() if half else e) + self.pos[pos:pos + n]).view(B * n, D)
-            if half:
-                y = _chain_half(h, stages, self.ln_f, self.dtype, st.kernels, select)
-                lg = F.linear(y.to(self.dtype), self.embed).float()
-            else:
-                y = _chain(h, stages, self.ln_f, _lib.add_layernorm if st.kernels else None, select)
-                lg = F.linear(y, self.embed)
+            h = self._embed(tok, self.pos[pos:pos + n]).view(B * n, D)
+            lg = self._project(_run_chain(h, stages, self.ln_f, self.dtype, st.kernels, select))
             if G > 1:  # the chunk's rows to its other beams
                 for cache in (*st.self_k, *st.self_v):
                     rows = cache.view(B, G, H, self.max_target_positions, 64)[:, :, :, pos:pos + n]
@@ -1051,96 +1057,141 @@ class WhisperDecoder:
             hyps = self.beam_search(encoder_states, prompt, eot, beam_size, patience, length_penalty, max_length,
                                     suppress_tokens, suppress_at_start, kernels, prefill, graph)
             return [h[0].ids if h else [] for h in hyps]
-        prompt = [int(t) for t in prompt]
-        eot = int(eot)
-        if not prompt:
-            raise ValueError("WhisperDecoder.generate: the prompt is empty")
-        if not 0 <= eot < self.V:
-            raise ValueError(f"WhisperDecoder.generate: eot {eot} is outside the vocabulary of {self.V}")
-        always, first = self._id_list(suppress_tokens, "suppress_tokens"), self._id_list(suppress_at_start, "suppress_at_start")
-        st = self.start(encoder_states, kernels, graph=graph)
-        B = st.B
-        ptok = self._tokens(torch.tensor(prompt).unsqueeze(0).expand(B, -1), (B, len(prompt)), "generate")
-        limit = min(int(max_length), self.max_target_positions)
-        if B == 0 or len(prompt) >= limit:
-            return [[] for _ in range(B)]
-        if prefill:
-            lg = self._prefill(st, ptok, False)
-        else:
-            for i in range(len(prompt)):
-                lg = self._step(st, ptok[:, i])
-        done = torch.zeros(B, dtype=torch.bool, device=self.device)
-        steps = []
-        while True:
+        prompt, eot = [int(t) for t in prompt], int(eot)
+        self._check_prompt("generate", prompt, eot)
+        always, first, st = self._open(encoder_states, suppress_tokens, suppress_at_start, kernels, 1, graph)
+        ptok = self._prompt_rows(st, prompt, "generate")
+        budget = self._budget(st, prompt, max_length)
+        if not budget:
+            return [[] for _ in range(st.B)]
+        lg, _ = self._feed_prompt(st, ptok, prefill)
+
+        def select(lg, n, done):
             if always is not None:
                 lg.index_fill_(1, always, float("-inf"))
-            if first is not None and not steps:
+            if first is not None and not n:
                 lg.index_fill_(1, first, float("-inf"))
             nxt = torch.where(done, eot, lg.argmax(-1))
-            steps.append(nxt)
-            done = done | (nxt == eot)
-            if len(prompt) + len(steps) >= limit or bool(done.all()):
-                break
-            if st.graph is not None:
-                steps = self._generate_on_device(st, nxt, done, always, eot, limit - len(prompt), int(sync_every))
-                break
-            lg = self._step(st, nxt)
-        out = []
-        for row in torch.stack(steps, 1).cpu().tolist():
-            out.append(row[:row.index(eot)] if eot in row else row)
-        return out
+            return nxt, done | (nxt == eot)
+
+        def fill(sel):
+            sel.suppress.zero_()
+            if always is not None:
+                sel.suppress.index_fill_(0, always, True)
+            sel.eot.fill_(eot)
+
+        rows = self._decode_rows(st, lg, budget, select, int(sync_every), "greedy", self._select_body, fill)
+        return [self._cut(row, eot) for row in rows]
+
+    # --------------------------------------------------- what generate, beam_search and sample share
+    def _check_prompt(self, who: str, prompt: list, eot: int) -> None:
+        if not prompt:
+            raise ValueError(f"WhisperDecoder.{who}: the prompt is empty")
+        if not 0 <= eot < self.V:
+            raise ValueError(f"WhisperDecoder.{who}: eot {eot} is outside the vocabulary of {self.V}")
+
+    def _open(self, encoder_states, suppress_tokens, suppress_at_start, kernels, beams: int, graph):
+        """-> (the ids of `suppress_tokens` and of `suppress_at_start` on the device or None, the
+        state of `start(beams=beams)`): what a decoding call sets up once its own arguments pass."""
+        always, first = self._id_list(suppress_tokens, "suppress_tokens"), self._id_list(suppress_at_start, "suppress_at_start")
+        return always, first, self.start(encoder_states, kernels, beams=beams, graph=graph)
+
+    def _budget(self, st: DecoderState, prompt: list, max_length) -> int:
+        """How many ids may be generated before prompt + generated ids number min(max_length,
+        max_target_positions); 0 for an empty batch too: nothing is decoded then."""
+        limit = min(int(max_length), self.max_target_positions)
+        return max(0, limit - len(prompt)) if st.B else 0
+
+    def _prompt_rows(self, st: DecoderState, prompt: list, who: str) -> torch.Tensor:
+        """The prompt as checked ids [rows, n], the same in every row of the state."""
+        return self._tokens(torch.tensor(prompt).unsqueeze(0).expand(st.rows, -1), (st.rows, len(prompt)), who)
+
+    @staticmethod
+    def _cut(row: list, eot: int) -> list:
+        """A row's generated ids up to its first `eot`."""
+        return row[:row.index(eot)] if eot in row else row
+
+    @staticmethod
+    def _rank(chunks: list, length_penalty: float = 1.0):
+        """Per chunk its (ids, sum, n) -> (per chunk its Hypotheses by score = sum / n **
+        length_penalty, the earlier first on ties; per chunk their n in the same order)."""
+        out, ns = [], []
+        for hyps in chunks:
+            ranked = [(Hypothesis(i, s, s / n ** float(length_penalty)), n) for i, s, n in hyps]
+            ranked.sort(key=lambda h: -h[0].score)  # (stable)
+            out.append([h for h, _ in ranked])
+            ns.append([n for _, n in ranked])
+        return out, ns
+
+    def _decode_rows(self, st: DecoderState, lg: torch.Tensor, budget: int, select, sync_every: int, *on_device) -> list:
+        """generate's and sample's loop from the logits after the prompt: select(lg, n, done) -> (the
+        ids [rows] of generated step n, `done` [rows] with the rows that ended on it), and the ids
+        are fed to the next step, until every row is done or `budget` ids are generated (the check
+        synchronises once per step).  On a graph state the steps after the first selection are
+        _decode_on_device's, `on_device` its last arguments.  Returns the ids per row, with
+        whatever a finished row was fed, as lists."""
+        with self._ctx():
+            done = torch.zeros(st.rows, dtype=torch.bool, device=self.device)
+            steps = []
+            while True:
+                nxt, done = select(lg, len(steps), done)
+                steps.append(nxt)
+                if len(steps) >= budget or bool(done.all()):
+                    break
+                if st.graph is not None:
+                    steps = self._decode_on_device(st, nxt, done, budget, sync_every, *on_device)
+                    break
+                lg = self._step(st, nxt)
+            return torch.stack(steps, 1).cpu().tolist()
 
     def _select_body(self, plan: _GraphPlan) -> None:
         """generate's selection on the plan's tensors: the logits buffer masked by `suppress`, the
         argmax (`eot` for the rows that are done), `done`, the ids into the token buffer and into
         row `count` of the record, count += 1."""
-        plan.logits.masked_fill_(plan.suppress, float("-inf"))
-        nxt = torch.where(plan.done, plan.eot, plan.logits.argmax(-1))
-        plan.done.logical_or_(nxt == plan.eot)
+        sel = plan.selection
+        plan.logits.masked_fill_(sel.suppress, float("-inf"))
+        nxt = torch.where(sel.done, sel.eot, plan.logits.argmax(-1))
+        sel.done.logical_or_(nxt == sel.eot)
         plan.tok.copy_(nxt)
-        plan.record.index_copy_(0, plan.count, nxt.unsqueeze(0))
-        plan.count.add_(1)
+        sel.record.index_copy_(0, sel.count, nxt.unsqueeze(0))
+        sel.count.add_(1)
 
-    def _generate_on_device(self, st: DecoderState, nxt: torch.Tensor, done: torch.Tensor, always, eot: int,
-                            budget: int, sync_every: int) -> list:
-        """generate's loop after the first selection (ids `nxt`, `done`; at least one row is live and
-        budget >= 2 ids may be generated in all): per step one replay of the step graph and one of
-        the selection graph, the completion asked of the device every `sync_every` generated steps.
-        Returns the ids of every step, the first included, as generate's `steps`."""
+    def _decode_on_device(self, st: DecoderState, nxt: torch.Tensor, done: torch.Tensor, budget: int, sync_every: int,
+                          key, body, fill, sums: Optional[torch.Tensor] = None) -> list:
+        """_decode_rows' loop after the first selection (ids `nxt`, `done`; at least one row is live
+        and budget >= 2 ids may be generated in all) on the plan's _Selection, made here at its
+        first use: per step one replay of the step graph and one of the selection graph `key`,
+        which is captured from body(plan) when the plan has none, and the completion asked of the
+        device every `sync_every` generated steps.  fill(selection) sets `suppress` (and `eot`);
+        `sums`: sample's running sums [rows], carried on in the selection's and updated at the end.
+        Returns the ids of every step, the first included."""
         plan = st.graph
         with self._ctx():
-            if plan.select is None:
-                dev, R = self.device, st.rows
-                plan.suppress = torch.zeros(self.V, dtype=torch.bool, device=dev)
-                plan.eot = torch.zeros(1, dtype=torch.int64, device=dev)
-                plan.done = torch.zeros(R, dtype=torch.bool, device=dev)
-                plan.count = torch.zeros(1, dtype=torch.int64, device=dev)
-                plan.record = torch.zeros((self.max_target_positions, R), dtype=torch.int64, device=dev)
-            plan.suppress.zero_()
-            if always is not None:
-                plan.suppress.index_fill_(0, always, True)
-            plan.eot.fill_(eot)
-            plan.done.copy_(done)
+            sel = plan.selection = plan.selection or _Selection(self, st.rows)
+            fill(sel)
+            sel.done.copy_(done)
+            state = (sel.done, sel.count, plan.tok)  # what body updates: a capture's warm-up must leave it as it is
+            if sums is not None:
+                sel.for_sample().sums.copy_(sums)
+                state = (sel.done, sel.sums, sel.count, plan.tok)
             plan.tok.copy_(nxt)
-            plan.record[0].copy_(nxt)
-            plan.count.fill_(1)
+            sel.record[0].copy_(nxt)
+            sel.count.fill_(1)
             n = 1
             while n < budget:
                 self._graph_step(st, None)  # at position len(prompt) + n - 1 <= limit - 2
-                if plan.select is None:  # once per plan; the warm-up's effects on the state are undone
-                    keep = [t.clone() for t in (plan.done, plan.count, plan.tok)]
-                    self._warm_up(self.device, lambda: self._select_body(plan))
-                    for t, k in zip((plan.done, plan.count, plan.tok), keep):
-                        t.copy_(k)
-                    g = torch.cuda.CUDAGraph()
-                    with self._capturing(g):
-                        self._select_body(plan)
-                    plan.select = g
-                plan.select.replay()
+                g = sel.graphs.get(key)
+                if g is None:  # once per plan and key
+                    if len(sel.graphs) >= _MAX_SELECT_GRAPHS:
+                        sel.graphs.clear()
+                    g = sel.graphs[key] = self._captured(lambda: body(plan), state=state)
+                g.replay()
                 n += 1
-                if n % sync_every == 0 and n < budget and bool(plan.done.all()):
+                if n % sync_every == 0 and n < budget and bool(sel.done.all()):
                     break
-            return list(plan.record[:n].unbind(0))
+            if sums is not None:
+                sums.copy_(sel.sums)
+            return list(sel.record[:n].unbind(0))
 
     def _select(self, lg: torch.Tensor, cum: torch.Tensor, G: int, kernels: bool):
         """wx_beam_topk's definition: per chunk the 2G best of cum[r] + log_softmax(lg[r])[t] as
@@ -1222,25 +1273,20 @@ class WhisperDecoder:
         same order, _feed_prompt's probabilities for `probe` or None)."""
         prompt = [int(t) for t in prompt]
         eot, G = int(eot), int(beam_size)
-        if not prompt:
-            raise ValueError("WhisperDecoder.beam_search: the prompt is empty")
-        if not 0 <= eot < self.V:
-            raise ValueError(f"WhisperDecoder.beam_search: eot {eot} is outside the vocabulary of {self.V}")
+        self._check_prompt("beam_search", prompt, eot)
         if not 1 <= G <= _MAX_BEAMS:
             raise ValueError(f"WhisperDecoder.beam_search: beam_size must lie in 1..{_MAX_BEAMS}, got {beam_size}")
         if not float(patience) > 0:
             raise ValueError(f"WhisperDecoder.beam_search: patience must be positive, got {patience}")
         if self.V < 2 * G:
             raise ValueError(f"WhisperDecoder.beam_search: a vocabulary of {self.V} is smaller than 2 x beam_size")
-        always, first = self._id_list(suppress_tokens, "suppress_tokens"), self._id_list(suppress_at_start, "suppress_at_start")
+        always, first, st = self._open(encoder_states, suppress_tokens, suppress_at_start, kernels, G, graph)
         max_finished = max(1, round(G * float(patience)))
-        st = self.start(encoder_states, kernels, beams=G, graph=graph)
         B, R, V = st.B, st.rows, self.V
-        limit = min(int(max_length), self.max_target_positions)
-        if B == 0 or len(prompt) >= limit:
+        budget = self._budget(st, prompt, max_length)
+        if not budget:
             return [[] for _ in range(B)], [[] for _ in range(B)], None
-        ptok = self._tokens(torch.tensor(prompt).unsqueeze(0).expand(R, -1), (R, len(prompt)), "beam_search")
-        lg, prob = self._feed_prompt(st, ptok, prefill, probe)
+        lg, prob = self._feed_prompt(st, self._prompt_rows(st, prompt, "beam_search"), prefill, probe)
         ninf = float("-inf")
         sums = [[0.0] + [ninf] * (G - 1) for _ in range(B)]
         ids = [[[] for _ in range(G)] for _ in range(B)]
@@ -1277,12 +1323,12 @@ class WhisperDecoder:
                 for j, (g, t, _) in enumerate(live):
                     parents[b * G + j], feed[b * G + j] = b * G + g, t
             done = all(len(f) >= max_finished for f in finished)
-            if len(prompt) + steps >= limit or done:
+            if steps >= budget or done:
                 break
             if parents != identity:
                 self.reorder(st, torch.tensor(parents, dtype=torch.int64))
             lg = self._step(st, torch.tensor(feed, dtype=torch.int64).to(self.device))
-        out, ns = [], []
+        chunks = []
         for b in range(B):
             hyps = list(finished[b])
             if len(hyps) < max_finished:  # not done: the live beams, already in order of their sums
@@ -1290,11 +1336,8 @@ class WhisperDecoder:
                     if len(hyps) >= G:
                         break
                     hyps.append((ids[b][g], sums[b][g], max(1, len(ids[b][g]))))
-            ranked = [(Hypothesis(i, s, s / n ** float(length_penalty)), n) for i, s, n in hyps]
-            ranked.sort(key=lambda h: -h[0].score)  # (stable: earlier-found first on ties)
-            out.append([h for h, _ in ranked])
-            ns.append([n for _, n in ranked])
-        return out, ns, prob
+            chunks.append(hyps)
+        return (*self._rank(chunks, length_penalty), prob)  # (the earlier-found first on ties)
 
     # ------------------------------------------------------------- sampling, temperature fallback
     def _select_token(self, lg: torch.Tensor, mask, temperature: float, seed: int, step: int, done: torch.Tensor,
@@ -1361,10 +1404,7 @@ class WhisperDecoder:
         order, _feed_prompt's probabilities for `probe` or None)."""
         prompt = [int(t) for t in prompt]
         eot, G, seed, T = int(eot), int(best_of), int(seed), float(temperature)
-        if not prompt:
-            raise ValueError("WhisperDecoder.sample: the prompt is empty")
-        if not 0 <= eot < self.V:
-            raise ValueError(f"WhisperDecoder.sample: eot {eot} is outside the vocabulary of {self.V}")
+        self._check_prompt("sample", prompt, eot)
         if not 1 <= G <= _MAX_BEAMS:
             raise ValueError(f"WhisperDecoder.sample: best_of must lie in 1..{_MAX_BEAMS}, got {best_of}")
         if not (T >= 0 and T != float("inf")):
@@ -1375,14 +1415,12 @@ class WhisperDecoder:
             raise ValueError(f"WhisperDecoder.sample: seed must be an unsigned 64-bit integer, got {seed}")
         if int(sync_every) < 1:
             raise ValueError(f"WhisperDecoder.sample: sync_every must be at least 1, got {sync_every}")
-        always, first = self._id_list(suppress_tokens, "suppress_tokens"), self._id_list(suppress_at_start, "suppress_at_start")
-        st = self.start(encoder_states, kernels, beams=G, graph=graph)
+        always, first, st = self._open(encoder_states, suppress_tokens, suppress_at_start, kernels, G, graph)
         B, R, dev = st.B, st.rows, self.device
-        limit = min(int(max_length), self.max_target_positions)
-        if B == 0 or len(prompt) >= limit:
+        budget = self._budget(st, prompt, max_length)
+        if not budget:
             return [[Hypothesis([], 0.0, 0.0) for _ in range(G)] for _ in range(B)], [[1] * G for _ in range(B)], None
-        ptok = self._tokens(torch.tensor(prompt).unsqueeze(0).expand(R, -1), (R, len(prompt)), "sample")
-        lg, prob = self._feed_prompt(st, ptok, prefill, probe)
+        lg, prob = self._feed_prompt(st, self._prompt_rows(st, prompt, "sample"), prefill, probe)
         with self._ctx():
             mask = mask0 = None
             if always is not None or first is not None:
@@ -1392,89 +1430,39 @@ class WhisperDecoder:
                     mask0 = mask.clone()
                 if first is not None:
                     mask0.index_fill_(0, first, True)
-            done = torch.zeros(R, dtype=torch.bool, device=dev)
             sums = torch.zeros(R, dtype=torch.float32, device=dev)
-            counter = torch.arange(limit, dtype=torch.int64, device=dev)  # element n: the step counter of step n
-            steps = []
-            while True:
-                n = len(steps)
-                if st.kernels:
-                    nxt, _ = _lib.sample_token(lg, counter[n:], eot, done, T, seed, mask if n else mask0, sums)
-                else:
-                    nxt, _ = self._select_token(lg, mask if n else mask0, T, seed, n, done, sums, eot)
-                steps.append(nxt)
-                if len(prompt) + len(steps) >= limit or bool(done.all()):
-                    break
-                if st.graph is not None:
-                    steps, sums = self._sample_on_device(st, nxt, done, sums, mask, eot, T, seed, limit - len(prompt),
-                                                         int(sync_every))
-                    break
-                lg = self._step(st, nxt)
-            rows, totals = torch.stack(steps, 1).cpu().tolist(), sums.cpu().tolist()
-        out, ns = [], []
-        for b in range(B):
-            ranked = []
-            for row, total in zip(rows[b * G:(b + 1) * G], totals[b * G:(b + 1) * G]):
-                ids = row[:row.index(eot)] if eot in row else row
-                n = max(1, len(ids) + (eot in row))
-                ranked.append((Hypothesis(ids, total, total / n), n))
-            ranked.sort(key=lambda h: -h[0].score)  # (stable: the earlier row first on ties)
-            out.append([h for h, _ in ranked])
-            ns.append([n for _, n in ranked])
-        return out, ns, prob
+            counter = torch.arange(len(prompt) + budget, dtype=torch.int64, device=dev)  # element n: the step counter of step n
+        key = (eot, T, seed)  # arguments of wx_sample_token's launch, and so part of a captured selection
+
+        def select(lg, n, done):  # (the kernel and its definition update done and sums in place)
+            if st.kernels:
+                return _lib.sample_token(lg, counter[n:], eot, done, T, seed, mask if n else mask0, sums)[0], done
+            return self._select_token(lg, mask if n else mask0, T, seed, n, done, sums, eot)[0], done
+
+        def fill(sel):
+            if mask is None:
+                sel.suppress.zero_()
+            else:
+                sel.suppress.copy_(mask)
+
+        rows = self._decode_rows(st, lg, budget, select, int(sync_every), key, lambda plan: self._sample_body(plan, *key),
+                                 fill, sums)
+        totals = sums.cpu().tolist()
+        chunks = [[] for _ in range(B)]
+        for r, (row, total) in enumerate(zip(rows, totals)):
+            ids = self._cut(row, eot)
+            chunks[r // G].append((ids, total, max(1, len(ids) + (eot in row))))
+        return (*self._rank(chunks), prob)  # (the earlier row first on ties)
 
     def _sample_body(self, plan: _GraphPlan, eot: int, temperature: float, seed: int) -> None:
         """sample's selection on the plan's tensors: wx_sample_token on the logits buffer with the
         step counter `count` read on the device, the ids straight into the step's token buffer,
         then into row `count` of the record, count += 1."""
-        sm = plan.sample
+        sm = plan.selection
         _lib.sample_token(plan.logits, sm.count, eot, sm.done, temperature, seed, sm.suppress, sm.sums, token=plan.tok,
                           logprob=sm.logprob, workspace=sm.ws)
         sm.record.index_copy_(0, sm.count, plan.tok.unsqueeze(0))
         sm.count.add_(1)
-
-    def _sample_on_device(self, st: DecoderState, nxt: torch.Tensor, done: torch.Tensor, sums: torch.Tensor, mask,
-                          eot: int, temperature: float, seed: int, budget: int, sync_every: int):
-        """sample's loop after the first selection, as _generate_on_device is generate's: per step
-        one replay of the step graph and one of the selection graph captured for (eot, temperature,
-        seed), which are arguments of the launch and so part of the graph.  Returns (the ids of
-        every step, the first included; the rows' sums)."""
-        plan = st.graph
-        with self._ctx():
-            if plan.sample is None:
-                plan.sample = _SampleTensors(self, st.rows)
-            sm = plan.sample
-            if mask is None:
-                sm.suppress.zero_()
-            else:
-                sm.suppress.copy_(mask)
-            sm.done.copy_(done)
-            sm.sums.copy_(sums)
-            plan.tok.copy_(nxt)
-            sm.record[0].copy_(nxt)
-            sm.count.fill_(1)
-            key = (eot, temperature, seed)
-            n = 1
-            while n < budget:
-                self._graph_step(st, None)  # at position len(prompt) + n - 1 <= limit - 2
-                g = sm.graphs.get(key)
-                if g is None:  # once per plan and key; the warm-up's effects on the state are undone
-                    state = (sm.done, sm.sums, sm.count, plan.tok)
-                    keep = [t.clone() for t in state]
-                    self._warm_up(self.device, lambda: self._sample_body(plan, *key))
-                    for t, k in zip(state, keep):
-                        t.copy_(k)
-                    g = torch.cuda.CUDAGraph()
-                    with self._capturing(g):
-                        self._sample_body(plan, *key)
-                    if len(sm.graphs) >= _MAX_SELECT_GRAPHS:
-                        sm.graphs.clear()
-                    sm.graphs[key] = g
-                g.replay()
-                n += 1
-                if n % sync_every == 0 and n < budget and bool(sm.done.all()):
-                    break
-            return list(sm.record[:n].unbind(0)), sm.sums.clone()
 
     @torch.inference_mode()
     def decode_with_fallback(self, encoder_states: torch.Tensor, prompt, eot: int,
