@@ -49,6 +49,8 @@
  *   wx_sample_token   <- whisperx/asr.py:305-312  temperatures, log_prob_threshold (the selection
  *                        of one greedy or sampled step with the token's log-probability: the
  *                        passes of the temperature fallback)
+ *   wx_penalize_logits <- whisperx/asr.py:302-303  repetition_penalty, no_repeat_ngram_size (a
+ *                        step's logits rewritten in place from the ids decoded so far)
  *
  * Conventions
  *   - All data pointers are DEVICE pointers (allocated by the caller; the library never
@@ -748,6 +750,40 @@ int wx_sample_token(const float* logits, int64_t row_stride, int32_t R, int32_t 
                     float temperature, uint64_t seed, const int64_t* step, int64_t eot, uint8_t* done,
                     int64_t* token, float* logprob, float* sum_logprob, void* workspace, size_t workspace_bytes,
                     void* stream);
+
+/* The repetition penalty and the no-repeat n-gram ban of one decoding step (WhisperDecoder's
+ * repetition_penalty and no_repeat_ngram_size), applied in place to R rows of V fp32 logits at
+ * logits + r row_stride ahead of the selection.  Row r's history is
+ *     h_i = history[i step_stride + r hist_row_stride], i in [0, L),
+ *     L = min(max(*count + count_offset, 0), max_history),
+ * with *count read on the device (so a captured launch sees a longer history at every replay) and
+ * the sum taken in 64 bits.  Both layouts are the strides' choice: step-major [L][R] is
+ * (R, 1), row-major [R][cap] is (1, cap).  An id outside [0, V) is skipped: it matches nothing and
+ * writes nothing (ids are compared as 64-bit values; they are narrowed only after the range check).
+ *   repetition penalty rho = repetition_penalty:
+ *     for every distinct in-range id t of the history, once however often it occurs:
+ *         x = logits[r][t];  logits[r][t] = x < 0 ? x rho : x / rho
+ *     in fp32: one multiplication or one correctly rounded division.  -inf stays -inf, -0 stays -0
+ *     (it is not below 0: it is divided).  rho == 1 writes nothing.
+ *   no-repeat n-gram, n = no_repeat_ngram_size:
+ *     n == 0: nothing.  n >= 1: for every j in [0, L - n] (none when L < n) with
+ *         h[j .. j + n - 2] == h[L - n + 1 .. L - 1]
+ *     logits[r][h[j + n - 1]] = -inf.  For n == 1 the comparison is empty, so every history id is
+ *     banned.  Matches that overlap the suffix count.  A skipped id inside either window makes the
+ *     window match nothing, and a skipped h[j + n - 1] bans nothing.
+ *   A ban wins over the penalty on the same column: the column is -inf.
+ * Columns that neither rule names, columns >= V and everything outside the R rows are never written
+ * (nor read).  A named column is stored once.  Row r's result is bit-identical whatever R is and
+ * whatever the other rows hold.  One launch, one workgroup per row; no workspace, no atomics.
+ * R < 0, V < 1 or V > 2^24, row_stride < V, a repetition_penalty that is not finite or not above 0,
+ * n < 0, max_history outside [0, WX_PENALTY_MAX_HISTORY]: WX_E_INVALID; then R == 0 or
+ * max_history == 0: WX_OK; then a null pointer or R above 65535 (a grid dimension): WX_E_INVALID;
+ * all before anything is enqueued.  The strides are the caller's: every h_i above must lie in
+ * history's allocation. */
+#define WX_PENALTY_MAX_HISTORY 1024
+int wx_penalize_logits(float* logits, int64_t row_stride, int32_t R, int32_t V, const int64_t* history,
+                       int64_t step_stride, int64_t hist_row_stride, const int64_t* count, int32_t count_offset,
+                       int32_t max_history, float repetition_penalty, int32_t no_repeat_ngram_size, void* stream);
 
 #ifdef __cplusplus
 }

@@ -69,6 +69,14 @@ positions, 1500 encoder positions:
     the same run, `sample` of 64 tokens x 16 chunks x best_of 5 at temperature 0.6 against
     `beam_search` at --beams and greedy `generate`, each direct and with graph=True.
 
+(h) --arms penalty (its own record, profiles/whisper_penalty_<host>.json): repetition_penalty and
+    no_repeat_ngram_size.  The rewrite alone, wx_penalize_logits (rho 1.1, n 3) on [16, 51865] and
+    [80, 51865] logits under histories of 32, 224 and 447 ids, against the torch chain it replaces:
+    transformers' RepetitionPenaltyLogitsProcessor and NoRepeatNGramLogitsProcessor on the same
+    device tensors (the second walks every row's ids on the host).  Then, fp32 with graph=True,
+    `generate` and `sample` (best_of 5, temperature 0.6) of 64 tokens x 16 chunks with the options
+    off, on, and off again in the same run.
+
 Prints one JSON line; --out writes it to a file (profiles/whisper_decoder_<host>.json).
 """
 from __future__ import annotations
@@ -822,6 +830,100 @@ def sample_arm(name, g, args, torch, _lib, dev):
     return r
 
 
+PENALTY = dict(repetition_penalty=1.1, no_repeat_ngram_size=3)
+
+
+def penalty_kernel_rows(args, torch, _lib, dev):
+    """(h): the rewrite launch against transformers' two processors, per row count and history length."""
+    from transformers import NoRepeatNGramLogitsProcessor, RepetitionPenaltyLogitsProcessor
+
+    rho, n = PENALTY["repetition_penalty"], PENALTY["no_repeat_ngram_size"]
+    chain_of = (RepetitionPenaltyLogitsProcessor(penalty=rho), NoRepeatNGramLogitsProcessor(n))
+    rows = []
+    for R in (CHUNKS, CHUNKS * 5):
+        base = 3 * torch.randn((R, V), device=dev)
+        ring = [base.clone() for _ in range(8)]
+        for L in (32, 224, 447):
+            ids = torch.randint(0, 300, (R, L), device=dev)  # few ids: trigrams do repeat
+            hist = ids.t().contiguous()
+            count = torch.tensor([L], dtype=torch.int64, device=dev)
+
+            def kernel(i):
+                return _lib.penalize_logits(ring[i % 8], hist, count, 0, L, rho, n)
+
+            def chain(i):
+                x = ring[i % 8]
+                for processor in chain_of:
+                    x = processor(ids, x)
+                return x
+
+            with torch.inference_mode():
+                want = chain_of[1](ids, chain_of[0](ids, base))
+                got = kernel_once(kernel, ring, base)
+                # (the chain divides by a host scalar, which the device backend may turn into a reciprocal: one ulp)
+                row = {"rows": R, "vocab": V, "history": L, "equal_to_chain": bool(torch.equal(got, want)),
+                       "max_abs_diff_to_chain": float(torch.nan_to_num(got - want, nan=0.0).abs().max()),
+                       "banned_columns": int(torch.isneginf(want).sum())}
+                row["wx_penalize_logits"] = event_timed(kernel, args.repeat, args.warmup, args.steps, torch)
+                for t in ring:  # (the kernel rewrote them in place, launch after launch)
+                    t.copy_(base)
+                row["torch_chain"] = event_timed(chain, args.repeat, args.warmup, min(args.steps, 10), torch)
+            row["kernel_vs_chain"] = beats(row["wx_penalize_logits"], row["torch_chain"])
+            rows.append(row)
+            print(f"penalty kernel: {R} rows, history {L} timed", file=sys.stderr, flush=True)
+        del ring, base
+        torch.cuda.empty_cache()
+    return rows
+
+
+def kernel_once(kernel, ring, base):
+    """One launch on a fresh copy of `base` (slot 0 of the ring) -> the rewritten logits."""
+    ring[0].copy_(base)
+    out = kernel(0).clone()
+    ring[0].copy_(base)
+    return out
+
+
+def penalty_arm(name, g, args, torch, _lib, dev):
+    """(h) for one geometry: generate and sample with graph=True, the options off, on and off again."""
+    from transformers import WhisperConfig, WhisperForConditionalGeneration
+
+    from whisperx_amd import WhisperDecoder
+
+    D, H = g["D"], g["D"] // 64
+    sync = torch.cuda.synchronize
+    eot = V - 1
+    r = {"shape": {**g, "heads": H, "vocab": V, "max_target_positions": T, "encoder_positions": P}, "best_of": 5,
+         "temperature": 0.6, "options": PENALTY}
+    cfg = WhisperConfig(d_model=D, encoder_layers=1, encoder_attention_heads=1, encoder_ffn_dim=64, num_mel_bins=80,
+                        max_source_positions=P, decoder_layers=g["layers"], decoder_attention_heads=H,
+                        decoder_ffn_dim=4 * D, vocab_size=V, max_target_positions=T, pad_token_id=0, bos_token_id=1,
+                        eos_token_id=2, decoder_start_token_id=1)
+    hf = WhisperForConditionalGeneration(cfg).eval().model.decoder
+    for p in hf.parameters():
+        p.requires_grad_(False)
+    enc = torch.randn((CHUNKS, P, D), device=dev)
+    prompt = PROMPT + [50363]
+    kw = dict(max_length=len(prompt) + N_TOKENS, suppress_tokens=[eot], graph=True)
+    dec = WhisperDecoder(hf, device=dev)
+    for what, call in (("generate", lambda **o: dec.generate(enc, prompt, eot, **kw, **o)),
+                       ("sample_best_of_5", lambda **o: dec.sample(enc, prompt, eot, temperature=0.6, best_of=5, seed=3, **kw, **o))):
+        on, off = call(**PENALTY), call()
+        row = {"chunks": CHUNKS, "generated_tokens": N_TOKENS, "options_change_the_result": on != off}
+        row["off"] = timed(lambda: call(), args.repeat, args.warmup, sync)
+        row["on"] = timed(lambda: call(**PENALTY), args.repeat, args.warmup, sync)
+        row["off_again"] = timed(lambda: call(), args.repeat, args.warmup, sync)
+        row["on_vs_off"] = beats(row["on"], row["off"])
+        row["on_minus_off_per_token_s"] = (row["on"]["median_s"] - row["off"]["median_s"]) / N_TOKENS
+        r[what] = row
+        print(f"{name}: {what} timed", file=sys.stderr, flush=True)
+    r["graph_captures"] = dec.graph_captures
+    dec.release_graphs()
+    del dec, hf, enc
+    torch.cuda.empty_cache()
+    return r
+
+
 def step_once(dec, enc, tok, torch):
     """The logits of a direct state's step at STEP_POS after STEP_POS steps on `tok`."""
     st = dec.start(enc)
@@ -834,8 +936,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", default="float32", choices=["float32", "float16", "bfloat16"],
                     help="float16 / bfloat16: (d), the half route's record (profiles/whisper_decoder_half*_<host>.json)")
-    ap.add_argument("--arms", default="decoder", choices=["decoder", "beam", "prefill", "graph", "sample"],
-                    help="(a) and (b), (c), (e), (f) or (g)")
+    ap.add_argument("--arms", default="decoder", choices=["decoder", "beam", "prefill", "graph", "sample", "penalty"],
+                    help="(a) and (b), (c), (e), (f), (g) or (h)")
     ap.add_argument("--beams", type=int, default=5)
     ap.add_argument("--geometries", default="base,large-v2")
     ap.add_argument("--repeat", type=int, default=5)
@@ -877,6 +979,13 @@ def main():
         for name in args.geometries.split(","):
             torch.manual_seed(args.seed)
             result["geometries"][name] = sample_arm(name, GEOMETRIES[name], args, torch, _lib, dev)
+        args.geometries = ""
+    if args.arms == "penalty":
+        torch.manual_seed(args.seed)
+        result["kernel"] = penalty_kernel_rows(args, torch, _lib, dev)
+        for name in args.geometries.split(","):
+            torch.manual_seed(args.seed)
+            result["geometries"][name] = penalty_arm(name, GEOMETRIES[name], args, torch, _lib, dev)
         args.geometries = ""
     eot = V - 1  # suppressed: both greedy loops run their full length
     if args.dtype != "float32":

@@ -28,7 +28,7 @@ SRC_PATHS = [SRC_PATH, os.path.join(_HERE, "csrc", "wx_binarize.hip"), os.path.j
              os.path.join(_HERE, "csrc", "wx_mel.hip"), os.path.join(_HERE, "csrc", "wx_whisper.hip"),
              os.path.join(_HERE, "csrc", "wx_decode.hip"), os.path.join(_HERE, "csrc", "wx_beam.hip"),
              os.path.join(_HERE, "csrc", "wx_attention_h16.hip"), os.path.join(_HERE, "csrc", "wx_prefill.hip"),
-             os.path.join(_HERE, "csrc", "wx_sample.hip")]
+             os.path.join(_HERE, "csrc", "wx_sample.hip"), os.path.join(_HERE, "csrc", "wx_penalty.hip")]
 INST_PATH = os.path.join(_HERE, "csrc", "wx_align_inst.hip")
 HDR_PATHS = sorted(glob.glob(os.path.join(_HERE, "csrc", "*.h"))) + [INST_PATH]  # (a new header: a rebuild)
 INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
@@ -139,6 +139,7 @@ SIGNATURES = {
     "wx_sample_token_workspace_bytes": (_sz, [_i32, _i32]),
     "wx_sample_token": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _f32, ctypes.c_uint64, _vp, _i64, _vp, _vp, _vp, _vp,
                                        _vp, _sz, _vp]),
+    "wx_penalize_logits": (ctypes.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _i64, _vp, _i32, _i32, _f32, _i32, _vp]),
 }
 
 
@@ -870,6 +871,48 @@ def sample_token(logits: torch.Tensor, step: torch.Tensor, eot: int, done: torch
                                    _ptr(logprob), _ptr(sum_logprob), _ptr(ws), ws.numel(),
                                    ctypes.c_void_p(stream.cuda_stream)))
     return token, logprob
+
+
+PENALTY_MAX_HISTORY = 1024  # WX_PENALTY_MAX_HISTORY: the longest history wx_penalize_logits reads
+
+
+def penalize_logits(logits: torch.Tensor, history: torch.Tensor, count: torch.Tensor, count_offset: int = 0,
+                    max_history: Optional[int] = None, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
+                    row_major: bool = False) -> torch.Tensor:
+    """wx_penalize_logits: logits [R, V] fp32 (any row stride >= V, columns contiguous), rewritten in
+    place and returned.  `history`: an int64 tensor of two dimensions on the logits' device, any
+    strides: [steps, R] (element [i, r] is id i of row r: the decoder's record), or with `row_major`
+    [R, steps].  `count`: an int64 device tensor whose first element, plus `count_offset`, is the
+    history's length, read on the device and clamped to [0, max_history]; `max_history` defaults
+    to the steps the tensor holds, at most PENALTY_MAX_HISTORY, and may not exceed either.  Every
+    distinct id of the history in [0, V) has its logit multiplied (below 0) or divided by
+    `repetition_penalty`, and with n = `no_repeat_ngram_size` >= 1 every id that would repeat an
+    n-gram of the history is set to -inf (include/wx_align.h states both).  On the current stream."""
+    lib = load()
+    if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_cuda:
+        raise WXError(f"penalize_logits: logits must be a float32 [R, V] device tensor, got {logits.dtype} "
+                      f"{tuple(logits.shape)}")
+    dev = logits.device
+    R, V = int(logits.shape[0]), int(logits.shape[1])
+    if V > 1 and logits.stride(1) != 1:
+        raise WXError("penalize_logits: the logits' columns must be contiguous")
+    if history.dim() != 2 or history.dtype != torch.int64 or history.device != dev:
+        raise WXError("penalize_logits: history must be an int64 tensor of two dimensions on the logits' device")
+    steps_dim, rows_dim = (1, 0) if row_major else (0, 1)
+    if int(history.shape[rows_dim]) != R:
+        raise WXError(f"penalize_logits: history {tuple(history.shape)} does not hold {R} rows")
+    steps = int(history.shape[steps_dim])
+    cap = min(steps, PENALTY_MAX_HISTORY) if max_history is None else int(max_history)
+    if cap > steps:
+        raise WXError(f"penalize_logits: max_history {cap} is more than the {steps} steps history holds")
+    if count.dtype != torch.int64 or count.device != dev or count.numel() < 1 or not count.is_contiguous():
+        raise WXError("penalize_logits: count must be a contiguous int64 tensor on the logits' device")
+    with torch.cuda.device(dev):
+        _check(lib.wx_penalize_logits(_ptr(logits), int(logits.stride(0)) if R > 1 else V, R, V, _ptr(history),
+                                      int(history.stride(steps_dim)), int(history.stride(rows_dim)), _ptr(count),
+                                      int(count_offset), cap, float(repetition_penalty), int(no_repeat_ngram_size),
+                                      _stream(dev)))
+    return logits
 
 
 def sincnet_stage(x_tm: torch.Tensor, do_abs: bool, gamma, beta, eps: float, slope: float = 0.01,

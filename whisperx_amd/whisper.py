@@ -48,8 +48,10 @@ as the rows of a `start(beams=best_of)` state, every selection one wx_sample_tok
 the argmax or the Gumbel-max draw from a counter-based generator keyed on (seed, row, step), the
 token's log-probability at temperature 1, the done / eot handling), and `decode_with_fallback` is
 faster-whisper's generate_with_fallback on a batch: the chunks that fail a threshold are decoded
-again at the next temperature.  Timestamps, the tokenizer, condition_on_previous_text,
-repetition_penalty / no_repeat_ngram_size and top-k / top-p truncation are not built.
+again at the next temperature.  `repetition_penalty` and `no_repeat_ngram_size` (asr.py:302-303)
+rewrite a step's logits ahead of every one of these selections from the ids decoded so far, one
+wx_penalize_logits launch on a history kept on the device (`_Penalty`).  Timestamps, the tokenizer,
+condition_on_previous_text and top-k / top-p truncation are not built.
 
 With `graph=True` (start, generate, beam_search, logits; off by default, HIP route only) a step is
 one replay of a captured graph: the self-attention is wx_decode_self_attention_f32 (_h16), which
@@ -513,6 +515,82 @@ def gumbel_uniforms(seed: int, R: int, V: int, step: int) -> np.ndarray:
     return ((x >> np.uint64(9)).astype(np.float64) + 0.5) * 2.0 ** -23
 
 
+def penalize_logits_host(lg: torch.Tensor, history: torch.Tensor, repetition_penalty: float,
+                         no_repeat_ngram_size: int) -> torch.Tensor:
+    """wx_penalize_logits' definition (include/wx_align.h) in torch ops, for the host route: lg [R, V]
+    fp32 rewritten in place, history [L, R] int64 (element [i, r] id i of row r; the decoder's ids,
+    all in [0, V): this route has no out-of-range id to skip).  Every history id's logit x becomes
+    x rho below 0, else x / rho (a true fp32 division: the divisor is a tensor, never a host scalar
+    that a backend may turn into a reciprocal), from the value read before any write, so an id that
+    occurs twice is penalised once; then the ids that would complete a repeated n-gram go to -inf."""
+    L, n = int(history.shape[0]), int(no_repeat_ngram_size)
+    if L and repetition_penalty != 1:
+        idx = history.t()
+        x = lg.gather(1, idx)
+        rho = torch.full_like(x, repetition_penalty)
+        lg.scatter_(1, idx, torch.where(x < 0, x * rho, x / rho))  # (equal ids carry equal values)
+    if n >= 1 and L >= n:
+        win = history.unfold(0, n, 1)  # [L - n + 1, R, n]: window j of row r
+        match = (win[:, :, :n - 1] == history[L - n + 1:].t()).all(-1)
+        j, r = match.nonzero(as_tuple=True)
+        lg[r, win[j, r, n - 1]] = float("-inf")
+    return lg
+
+
+class _Penalty:
+    """The one place where generate, beam_search and sample rewrite a step's logits by
+    repetition_penalty `rho` and no_repeat_ngram_size `n`: made by WhisperDecoder._penalty from the
+    checked arguments (None at the defaults, and then nothing below exists), bound to a state by
+    `bind`.  `hist` [max_target_positions, rows] int64 is the history, step-major as the selection's
+    record is: rows [0, P0) the prompt's part (`prefix`), row P0 + i the ids fed after generated
+    step i.  `counter`: element i is i, so counter[i:] is a device pointer to the count i for a
+    launch outside a graph, as sample's step counter is.  On a graph state `hist` is the
+    selection's own (`_Selection.for_penalty`), and hist[P0:] takes the place of its record."""
+
+    def __init__(self, rho: float, n: int, prefix: list):
+        self.rho, self.n, self.prefix, self.P0 = rho, n, prefix, len(prefix)
+        self.key = (rho, n, self.P0)  # what a captured launch is bound to
+        self.hist = self.counter = self.record = None
+        self.kernels, self.cap = False, 0
+
+    def bind(self, dec: "WhisperDecoder", st: "DecoderState") -> "_Penalty":
+        dev, T = dec.device, dec.max_target_positions
+        with dec._ctx():
+            if st.graph is not None:
+                plan = st.graph
+                plan.selection = plan.selection or _Selection(dec, st.rows)
+                self.hist = plan.selection.for_penalty()
+            else:
+                self.hist = torch.zeros((T, st.rows), dtype=torch.int64, device=dev)
+            if self.P0:
+                self.hist[:self.P0] = torch.tensor(self.prefix, dtype=torch.int64).to(dev)[:, None]
+            self.counter = torch.arange(T + 1, dtype=torch.int64, device=dev)
+        self.record = self.hist[self.P0:]
+        self.kernels, self.cap = st.kernels, min(T, _lib.PENALTY_MAX_HISTORY)
+        return self
+
+    def apply(self, lg: torch.Tensor, i: int) -> None:
+        """The logits of generated step i (i ids generated so far), rewritten in place."""
+        if self.kernels:
+            _lib.penalize_logits(lg, self.hist, self.counter[i:], self.P0, self.cap, self.rho, self.n)
+        else:
+            penalize_logits_host(lg, self.hist[:self.P0 + i], self.rho, self.n)
+
+    def apply_counted(self, lg: torch.Tensor, count: torch.Tensor) -> None:
+        """`apply` inside a captured selection: the count is the selection's, read on the device."""
+        _lib.penalize_logits(lg, self.hist, count, self.P0, self.cap, self.rho, self.n)
+
+    def append(self, i: int, ids: torch.Tensor) -> None:
+        """The ids [rows] chosen at generated step i join the history (no synchronisation)."""
+        self.record[i].copy_(ids)
+
+    def follow(self, parents: torch.Tensor, i: int) -> None:
+        """Row r's history before generated step i becomes row parents[r]'s, as `reorder` moves the
+        caches."""
+        live = self.hist[:self.P0 + i]
+        live.copy_(live.index_select(1, parents))
+
+
 class DecoderState:
     """What `WhisperDecoder.start` returns and `step` advances: per layer the cross-attention keys
     and values (`cross`: [B, P, 2D], the k half then the v half of one GEMM), the self-attention
@@ -565,8 +643,9 @@ class _Selection:
     wx_sample_token's step counter), `record` [max_target_positions, rows] int64 (the ids of every
     step), greedy's `eot` int64 [1], and `graphs`: the captured selections, greedy's one under
     "greedy" and sample's under (eot, temperature, seed), which are arguments of its launch; at
-    most _MAX_SELECT_GRAPHS in all.  Sample's own `sums` and `logprob` [rows] fp32 and its kernel's
-    workspace `ws` are made by `for_sample` at sample's first use."""
+    most _MAX_SELECT_GRAPHS in all (a penalised call's key also holds its _Penalty's).  Sample's own
+    `sums` and `logprob` [rows] fp32 and its kernel's workspace `ws` are made by `for_sample` at
+    sample's first use, and `history` by `for_penalty` at the first penalised call."""
 
     def __init__(self, dec: "WhisperDecoder", R: int):
         dev = dec.device
@@ -576,7 +655,14 @@ class _Selection:
         self.count = torch.zeros(1, dtype=torch.int64, device=dev)
         self.record = torch.zeros((dec.max_target_positions, R), dtype=torch.int64, device=dev)
         self.graphs = {}
-        self.sums = self.logprob = self.ws = None
+        self.sums = self.logprob = self.ws = self.history = None
+
+    def for_penalty(self) -> torch.Tensor:
+        """`history`, a second record [max_target_positions, rows] int64 made at the first penalised
+        call: a _Penalty's history, whose rows from the prompt's part on stand in for `record`."""
+        if self.history is None:
+            self.history = torch.zeros_like(self.record)
+        return self.history
 
     def for_sample(self) -> "_Selection":
         if self.ws is None:
@@ -1031,7 +1117,9 @@ class WhisperDecoder:
     @torch.inference_mode()
     def generate(self, encoder_states: torch.Tensor, prompt, eot: int, max_length: int = 448, suppress_tokens=(),
                  suppress_at_start=(), kernels: Optional[bool] = None, beam_size: int = 1, patience: float = 1.0,
-                 length_penalty: float = 1.0, prefill: bool = False, graph: bool = False, sync_every: int = 8) -> list:
+                 length_penalty: float = 1.0, prefill: bool = False, graph: bool = False, sync_every: int = 8,
+                 repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
+                 history_from: Optional[int] = None) -> list:
         """Greedy decoding (asr.py:53-62 at beam_size 1, temperature 0): `prompt` (a list of ids,
         the same for every row) is fed one id per step; then every step takes the argmax of the
         logits with `suppress_tokens` at -inf, and at the first generated position also
@@ -1050,28 +1138,55 @@ class WhisperDecoder:
         recording run on the device in a second small graph of the plan, and the host asks whether
         every row is done only every `sync_every` generated steps (and never replays at a position
         >= min(max_length, max_target_positions)).  Steps taken after every row finished feed
-        `eot` and are discarded, so the result equals graph=False token for token."""
+        `eot` and are discarded, so the result equals graph=False token for token.
+
+        `repetition_penalty` rho and `no_repeat_ngram_size` n (asr.py:302-303; faster-whisper hands
+        both to every pass): before the masks, every step's logits are rewritten from the row's
+        history by wx_penalize_logits' definition (include/wx_align.h; the same in torch ops on
+        the host route).  Every distinct id of the history has its logit x replaced by x rho
+        below 0 and x / rho otherwise, and with n >= 1 every id that would complete an n-gram the
+        history already holds goes to -inf.  The argmax, and in `sample` and `beam_search` the
+        draw, the log-probabilities and the sums, are those of the rewritten logits.  A row whose
+        logits are then all -inf ends as if it had chosen `eot`.  The history of a row is
+        prompt[history_from:] followed by its generated ids; `history_from` None (the default)
+        means the generated ids alone, 0 the whole prompt as transformers' generate counts it,
+        and any Python index into the prompt is accepted.  Which of the start ids CTranslate2
+        counts could not be checked against it (it is not a dependency of this package), so the
+        choice is the caller's.  At rho 1 and n 0 nothing is launched or allocated and the result is
+        bit for bit the unpenalised one.  On a graph state the rewrite is one more kernel of the
+        captured selection, reading the history's length from the selection's device counter."""
         if int(sync_every) < 1:
             raise ValueError(f"WhisperDecoder.generate: sync_every must be at least 1, got {sync_every}")
         if int(beam_size) != 1:
             hyps = self.beam_search(encoder_states, prompt, eot, beam_size, patience, length_penalty, max_length,
-                                    suppress_tokens, suppress_at_start, kernels, prefill, graph)
+                                    suppress_tokens, suppress_at_start, kernels, prefill, graph, repetition_penalty,
+                                    no_repeat_ngram_size, history_from)
             return [h[0].ids if h else [] for h in hyps]
         prompt, eot = [int(t) for t in prompt], int(eot)
         self._check_prompt("generate", prompt, eot)
+        pen = self._penalty("generate", prompt, max_length, repetition_penalty, no_repeat_ngram_size, history_from)
         always, first, st = self._open(encoder_states, suppress_tokens, suppress_at_start, kernels, 1, graph)
         ptok = self._prompt_rows(st, prompt, "generate")
         budget = self._budget(st, prompt, max_length)
         if not budget:
             return [[] for _ in range(st.B)]
         lg, _ = self._feed_prompt(st, ptok, prefill)
+        if pen is not None:
+            pen.bind(self, st)
 
         def select(lg, n, done):
+            if pen is not None:
+                pen.apply(lg, n)
             if always is not None:
                 lg.index_fill_(1, always, float("-inf"))
             if first is not None and not n:
                 lg.index_fill_(1, first, float("-inf"))
-            nxt = torch.where(done, eot, lg.argmax(-1))
+            best = lg.argmax(-1)
+            if pen is not None:  # (a row with nothing left ends)
+                done = done | (lg.gather(1, best[:, None])[:, 0] == float("-inf"))
+            nxt = torch.where(done, eot, best)
+            if pen is not None:
+                pen.append(n, nxt)
             return nxt, done | (nxt == eot)
 
         def fill(sel):
@@ -1080,7 +1195,9 @@ class WhisperDecoder:
                 sel.suppress.index_fill_(0, always, True)
             sel.eot.fill_(eot)
 
-        rows = self._decode_rows(st, lg, budget, select, int(sync_every), "greedy", self._select_body, fill)
+        key = "greedy" if pen is None else ("greedy", *pen.key)
+        rows = self._decode_rows(st, lg, budget, select, int(sync_every), key, lambda plan: self._select_body(plan, pen),
+                                 fill, None, pen)
         return [self._cut(row, eot) for row in rows]
 
     # --------------------------------------------------- what generate, beam_search and sample share
@@ -1089,6 +1206,30 @@ class WhisperDecoder:
             raise ValueError(f"WhisperDecoder.{who}: the prompt is empty")
         if not 0 <= eot < self.V:
             raise ValueError(f"WhisperDecoder.{who}: eot {eot} is outside the vocabulary of {self.V}")
+
+    def _penalty(self, who: str, prompt: list, max_length, repetition_penalty, no_repeat_ngram_size,
+                 history_from) -> Optional[_Penalty]:
+        """The checked repetition_penalty / no_repeat_ngram_size / history_from of a decoding call
+        (generate's docstring) as a _Penalty still to be bound, or None when they change nothing."""
+        with np.errstate(over="ignore"):
+            rho = float(np.float32(repetition_penalty))  # the value the kernel is handed
+        if not (rho > 0 and rho != float("inf")):
+            raise ValueError(f"WhisperDecoder.{who}: repetition_penalty must be finite and positive (in fp32), got "
+                             f"{repetition_penalty}")
+        n = no_repeat_ngram_size
+        if isinstance(n, bool) or int(n) != n or int(n) < 0 or int(n) >= 1 << 31:
+            raise ValueError(f"WhisperDecoder.{who}: no_repeat_ngram_size must be an integer of at least 0, got {n}")
+        if history_from is not None and not -len(prompt) <= int(history_from) <= len(prompt):
+            raise ValueError(f"WhisperDecoder.{who}: history_from {history_from} is no index into the prompt of "
+                             f"{len(prompt)} ids")
+        if rho == 1 and int(n) == 0:
+            return None
+        prefix = [] if history_from is None else prompt[int(history_from):]
+        longest = len(prefix) + max(0, min(int(max_length), self.max_target_positions) - len(prompt))
+        if longest > _lib.PENALTY_MAX_HISTORY:
+            raise ValueError(f"WhisperDecoder.{who}: history_from {history_from} and max_length {max_length} allow a "
+                             f"history of {longest} ids, more than the {_lib.PENALTY_MAX_HISTORY} the penalty reads")
+        return _Penalty(rho, int(n), prefix)
 
     def _open(self, encoder_states, suppress_tokens, suppress_at_start, kernels, beams: int, graph):
         """-> (the ids of `suppress_tokens` and of `suppress_at_start` on the device or None, the
@@ -1144,27 +1285,34 @@ class WhisperDecoder:
                 lg = self._step(st, nxt)
             return torch.stack(steps, 1).cpu().tolist()
 
-    def _select_body(self, plan: _GraphPlan) -> None:
+    def _select_body(self, plan: _GraphPlan, pen: Optional[_Penalty] = None) -> None:
         """generate's selection on the plan's tensors: the logits buffer masked by `suppress`, the
         argmax (`eot` for the rows that are done), `done`, the ids into the token buffer and into
-        row `count` of the record, count += 1."""
+        row `count` of the record, count += 1.  `pen`: the logits are rewritten by it first, its
+        history's length `count` plus its prompt part; a row left without a finite logit is done;
+        the ids go into its history, which is the record then."""
         sel = plan.selection
+        if pen is not None:
+            pen.apply_counted(plan.logits, sel.count)
         plan.logits.masked_fill_(sel.suppress, float("-inf"))
-        nxt = torch.where(sel.done, sel.eot, plan.logits.argmax(-1))
+        best = plan.logits.argmax(-1)
+        ended = sel.done if pen is None else sel.done | (plan.logits.gather(1, best[:, None])[:, 0] == float("-inf"))
+        nxt = torch.where(ended, sel.eot, best)
         sel.done.logical_or_(nxt == sel.eot)
         plan.tok.copy_(nxt)
-        sel.record.index_copy_(0, sel.count, nxt.unsqueeze(0))
+        (sel.record if pen is None else pen.record).index_copy_(0, sel.count, nxt.unsqueeze(0))
         sel.count.add_(1)
 
     def _decode_on_device(self, st: DecoderState, nxt: torch.Tensor, done: torch.Tensor, budget: int, sync_every: int,
-                          key, body, fill, sums: Optional[torch.Tensor] = None) -> list:
+                          key, body, fill, sums: Optional[torch.Tensor] = None, pen: Optional[_Penalty] = None) -> list:
         """_decode_rows' loop after the first selection (ids `nxt`, `done`; at least one row is live
         and budget >= 2 ids may be generated in all) on the plan's _Selection, made here at its
         first use: per step one replay of the step graph and one of the selection graph `key`,
         which is captured from body(plan) when the plan has none, and the completion asked of the
         device every `sync_every` generated steps.  fill(selection) sets `suppress` (and `eot`);
         `sums`: sample's running sums [rows], carried on in the selection's and updated at the end.
-        Returns the ids of every step, the first included."""
+        `pen`: the call's _Penalty, whose history the bodies record into (it is bound to the
+        selection's `history`).  Returns the ids of every step, the first included."""
         plan = st.graph
         with self._ctx():
             sel = plan.selection = plan.selection or _Selection(self, st.rows)
@@ -1174,8 +1322,11 @@ class WhisperDecoder:
             if sums is not None:
                 sel.for_sample().sums.copy_(sums)
                 state = (sel.done, sel.sums, sel.count, plan.tok)
+            record = sel.record
+            if pen is not None:  # (the rewrite is not idempotent as the mask is: the logits are state too)
+                record, state = pen.record, (*state, plan.logits)
             plan.tok.copy_(nxt)
-            sel.record[0].copy_(nxt)
+            record[0].copy_(nxt)
             sel.count.fill_(1)
             n = 1
             while n < budget:
@@ -1191,7 +1342,7 @@ class WhisperDecoder:
                     break
             if sums is not None:
                 sums.copy_(sel.sums)
-            return list(sel.record[:n].unbind(0))
+            return list(record[:n].unbind(0))
 
     def _select(self, lg: torch.Tensor, cum: torch.Tensor, G: int, kernels: bool):
         """wx_beam_topk's definition: per chunk the 2G best of cum[r] + log_softmax(lg[r])[t] as
@@ -1212,7 +1363,9 @@ class WhisperDecoder:
     @torch.inference_mode()
     def beam_search(self, encoder_states: torch.Tensor, prompt, eot: int, beam_size: int = 5, patience: float = 1.0,
                     length_penalty: float = 1.0, max_length: int = 448, suppress_tokens=(), suppress_at_start=(),
-                    kernels: Optional[bool] = None, prefill: bool = False, graph: bool = False) -> list:
+                    kernels: Optional[bool] = None, prefill: bool = False, graph: bool = False,
+                    repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
+                    history_from: Optional[int] = None) -> list:
         """Beam search (asr.py:301-304: the reference's default is beam_size 5, patience 1,
         length_penalty 1).  The structure is that of OpenAI's BeamSearchDecoder and
         MaximumLikelihoodRanker; this docstring is the specification.
@@ -1237,9 +1390,14 @@ class WhisperDecoder:
         the B chunks (a chunk's beams are identical during the prompt) instead of one step per id
         on B G rows; off by default, as in generate.  `graph`: the step on the B G rows is a
         replay of start's captured graph (HIP route only); the top-k, the host walk and `reorder`
-        are unchanged, and so are the hypotheses."""
+        are unchanged, and so are the hypotheses.  `repetition_penalty`, `no_repeat_ngram_size` and
+        `history_from` are generate's: every beam's logits are rewritten from that beam's own
+        history before the masks, so the candidates' scores and the hypotheses' sums are those of
+        the rewritten logits (a banned candidate scores -inf and ranks last, as a masked one does),
+        and the histories follow the beams whenever the caches do."""
         return self._beam_search(encoder_states, prompt, eot, beam_size, patience, length_penalty, max_length,
-                                 suppress_tokens, suppress_at_start, kernels, prefill, graph)[0]
+                                 suppress_tokens, suppress_at_start, kernels, prefill, graph,
+                                 penalty=(repetition_penalty, no_repeat_ngram_size, history_from))[0]
 
     def _feed_prompt(self, st: DecoderState, ptok: torch.Tensor, prefill: bool, probe=None):
         """The prompt ptok [rows, n] (the same ids in every row) into a fresh state, one step per id
@@ -1268,9 +1426,10 @@ class WhisperDecoder:
         return lg, prob
 
     def _beam_search(self, encoder_states, prompt, eot, beam_size, patience, length_penalty, max_length,
-                     suppress_tokens, suppress_at_start, kernels, prefill, graph, probe=None):
+                     suppress_tokens, suppress_at_start, kernels, prefill, graph, probe=None, penalty=(1.0, 0, None)):
         """beam_search -> (its result, per chunk the scored positions n of every hypothesis in the
-        same order, _feed_prompt's probabilities for `probe` or None)."""
+        same order, _feed_prompt's probabilities for `probe` or None).  `penalty`:
+        (repetition_penalty, no_repeat_ngram_size, history_from)."""
         prompt = [int(t) for t in prompt]
         eot, G = int(eot), int(beam_size)
         self._check_prompt("beam_search", prompt, eot)
@@ -1280,6 +1439,7 @@ class WhisperDecoder:
             raise ValueError(f"WhisperDecoder.beam_search: patience must be positive, got {patience}")
         if self.V < 2 * G:
             raise ValueError(f"WhisperDecoder.beam_search: a vocabulary of {self.V} is smaller than 2 x beam_size")
+        pen = self._penalty("beam_search", prompt, max_length, *penalty)
         always, first, st = self._open(encoder_states, suppress_tokens, suppress_at_start, kernels, G, graph)
         max_finished = max(1, round(G * float(patience)))
         B, R, V = st.B, st.rows, self.V
@@ -1287,6 +1447,8 @@ class WhisperDecoder:
         if not budget:
             return [[] for _ in range(B)], [[] for _ in range(B)], None
         lg, prob = self._feed_prompt(st, self._prompt_rows(st, prompt, "beam_search"), prefill, probe)
+        if pen is not None:
+            pen.bind(self, st)
         ninf = float("-inf")
         sums = [[0.0] + [ninf] * (G - 1) for _ in range(B)]
         ids = [[[] for _ in range(G)] for _ in range(B)]
@@ -1294,6 +1456,8 @@ class WhisperDecoder:
         steps = 0
         identity = list(range(R))
         while True:
+            if pen is not None:
+                pen.apply(lg, steps)
             if always is not None:
                 lg.index_fill_(1, always, ninf)
             if first is not None and not steps:
@@ -1325,9 +1489,14 @@ class WhisperDecoder:
             done = all(len(f) >= max_finished for f in finished)
             if steps >= budget or done:
                 break
+            feed = torch.tensor(feed, dtype=torch.int64).to(self.device)
             if parents != identity:
                 self.reorder(st, torch.tensor(parents, dtype=torch.int64))
-            lg = self._step(st, torch.tensor(feed, dtype=torch.int64).to(self.device))
+                if pen is not None:
+                    pen.follow(torch.tensor(parents, dtype=torch.int64).to(self.device), steps - 1)
+            if pen is not None:
+                pen.append(steps - 1, feed)
+            lg = self._step(st, feed)
         chunks = []
         for b in range(B):
             hyps = list(finished[b])
@@ -1367,7 +1536,9 @@ class WhisperDecoder:
     @torch.inference_mode()
     def sample(self, encoder_states: torch.Tensor, prompt, eot: int, temperature: float = 0.0, best_of: int = 1,
                seed: int = 0, max_length: int = 448, suppress_tokens=(), suppress_at_start=(),
-               kernels: Optional[bool] = None, prefill: bool = False, graph: bool = False, sync_every: int = 8) -> list:
+               kernels: Optional[bool] = None, prefill: bool = False, graph: bool = False, sync_every: int = 8,
+               repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
+               history_from: Optional[int] = None) -> list:
         """Greedy decoding or sampling with the sequences' log-probabilities (faster-whisper's
         `temperature` and `best_of`; one pass of decode_with_fallback).  Per chunk `best_of`
         candidates are decoded side by side as the rows b best_of + g of a `start(beams=best_of)`
@@ -1394,14 +1565,20 @@ class WhisperDecoder:
         from device memory, the ids into the token buffer and the record), and the host asks
         whether every row is done every `sync_every` generated steps; the result equals
         graph=False exactly, ids and sums.  A selection graph is captured per (temperature, seed,
-        eot) of a plan and kept; `graph_captures` counts step graphs only."""
+        eot) of a plan and kept; `graph_captures` counts step graphs only.  `repetition_penalty`,
+        `no_repeat_ngram_size` and `history_from` are generate's: every candidate's logits are
+        rewritten from its own history before the selection, which then masks, draws and scores
+        the rewritten logits (on a graph state one more launch of the captured selection, whose
+        key gains the three values' (rho, n, length of the prompt's part))."""
         return self._sample(encoder_states, prompt, eot, temperature, best_of, seed, max_length, suppress_tokens,
-                            suppress_at_start, kernels, prefill, graph, sync_every)[0]
+                            suppress_at_start, kernels, prefill, graph, sync_every,
+                            penalty=(repetition_penalty, no_repeat_ngram_size, history_from))[0]
 
     def _sample(self, encoder_states, prompt, eot, temperature, best_of, seed, max_length, suppress_tokens,
-                suppress_at_start, kernels, prefill, graph, sync_every, probe=None):
+                suppress_at_start, kernels, prefill, graph, sync_every, probe=None, penalty=(1.0, 0, None)):
         """sample -> (its result, per chunk the scored positions n of every hypothesis in the same
-        order, _feed_prompt's probabilities for `probe` or None)."""
+        order, _feed_prompt's probabilities for `probe` or None).  `penalty`: (repetition_penalty,
+        no_repeat_ngram_size, history_from)."""
         prompt = [int(t) for t in prompt]
         eot, G, seed, T = int(eot), int(best_of), int(seed), float(temperature)
         self._check_prompt("sample", prompt, eot)
@@ -1415,12 +1592,15 @@ class WhisperDecoder:
             raise ValueError(f"WhisperDecoder.sample: seed must be an unsigned 64-bit integer, got {seed}")
         if int(sync_every) < 1:
             raise ValueError(f"WhisperDecoder.sample: sync_every must be at least 1, got {sync_every}")
+        pen = self._penalty("sample", prompt, max_length, *penalty)
         always, first, st = self._open(encoder_states, suppress_tokens, suppress_at_start, kernels, G, graph)
         B, R, dev = st.B, st.rows, self.device
         budget = self._budget(st, prompt, max_length)
         if not budget:
             return [[Hypothesis([], 0.0, 0.0) for _ in range(G)] for _ in range(B)], [[1] * G for _ in range(B)], None
         lg, prob = self._feed_prompt(st, self._prompt_rows(st, prompt, "sample"), prefill, probe)
+        if pen is not None:
+            pen.bind(self, st)
         with self._ctx():
             mask = mask0 = None
             if always is not None or first is not None:
@@ -1433,11 +1613,19 @@ class WhisperDecoder:
             sums = torch.zeros(R, dtype=torch.float32, device=dev)
             counter = torch.arange(len(prompt) + budget, dtype=torch.int64, device=dev)  # element n: the step counter of step n
         key = (eot, T, seed)  # arguments of wx_sample_token's launch, and so part of a captured selection
+        if pen is not None:
+            key += pen.key
 
         def select(lg, n, done):  # (the kernel and its definition update done and sums in place)
+            if pen is not None:
+                pen.apply(lg, n)
             if st.kernels:
-                return _lib.sample_token(lg, counter[n:], eot, done, T, seed, mask if n else mask0, sums)[0], done
-            return self._select_token(lg, mask if n else mask0, T, seed, n, done, sums, eot)[0], done
+                tok = _lib.sample_token(lg, counter[n:], eot, done, T, seed, mask if n else mask0, sums)[0]
+            else:
+                tok = self._select_token(lg, mask if n else mask0, T, seed, n, done, sums, eot)[0]
+            if pen is not None:
+                pen.append(n, tok)
+            return tok, done
 
         def fill(sel):
             if mask is None:
@@ -1445,8 +1633,8 @@ class WhisperDecoder:
             else:
                 sel.suppress.copy_(mask)
 
-        rows = self._decode_rows(st, lg, budget, select, int(sync_every), key, lambda plan: self._sample_body(plan, *key),
-                                 fill, sums)
+        rows = self._decode_rows(st, lg, budget, select, int(sync_every), key,
+                                 lambda plan: self._sample_body(plan, eot, T, seed, pen), fill, sums, pen)
         totals = sums.cpu().tolist()
         chunks = [[] for _ in range(B)]
         for r, (row, total) in enumerate(zip(rows, totals)):
@@ -1454,14 +1642,17 @@ class WhisperDecoder:
             chunks[r // G].append((ids, total, max(1, len(ids) + (eot in row))))
         return (*self._rank(chunks), prob)  # (the earlier row first on ties)
 
-    def _sample_body(self, plan: _GraphPlan, eot: int, temperature: float, seed: int) -> None:
+    def _sample_body(self, plan: _GraphPlan, eot: int, temperature: float, seed: int,
+                     pen: Optional[_Penalty] = None) -> None:
         """sample's selection on the plan's tensors: wx_sample_token on the logits buffer with the
         step counter `count` read on the device, the ids straight into the step's token buffer,
-        then into row `count` of the record, count += 1."""
+        then into row `count` of the record, count += 1.  `pen`: as in _select_body."""
         sm = plan.selection
+        if pen is not None:
+            pen.apply_counted(plan.logits, sm.count)
         _lib.sample_token(plan.logits, sm.count, eot, sm.done, temperature, seed, sm.suppress, sm.sums, token=plan.tok,
                           logprob=sm.logprob, workspace=sm.ws)
-        sm.record.index_copy_(0, sm.count, plan.tok.unsqueeze(0))
+        (sm.record if pen is None else pen.record).index_copy_(0, sm.count, plan.tok.unsqueeze(0))
         sm.count.add_(1)
 
     @torch.inference_mode()
@@ -1472,7 +1663,8 @@ class WhisperDecoder:
                              sot_index: int = 0, compression_ratio_threshold: Optional[float] = 2.4, text_of=None,
                              seed: int = 0, max_length: int = 448, suppress_tokens=(), suppress_at_start=(),
                              kernels: Optional[bool] = None, prefill: bool = False, graph: bool = False,
-                             sync_every: int = 8) -> list:
+                             sync_every: int = 8, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
+                             history_from: Optional[int] = None) -> list:
         """Temperature fallback (asr.py:305-312: temperatures 0 .. 1, compression_ratio_threshold
         2.4, log_prob_threshold -1, no_speech_threshold 0.6): faster-whisper's
         generate_with_fallback on a batch of chunks; this docstring is the specification.
@@ -1497,7 +1689,10 @@ class WhisperDecoder:
         its attempt with the highest avg_logprob, the earliest on ties.  `no_speech_prob` is
         softmax(logits after prompt[sot_index])[no_speech_token] over the whole vocabulary, read
         during the first pass's prompt (with `prefill` the prompt is then fed in two pieces, around
-        sot_index); None when `no_speech_token` is None.  The remaining arguments are generate's.
+        sot_index); None when `no_speech_token` is None.  The remaining arguments are generate's;
+        `repetition_penalty`, `no_repeat_ngram_size` and `history_from` go to every pass, as
+        faster-whisper hands them to every generate call of its loop (the no-speech probability is
+        read during the prompt, before any rewrite).
 
         Returns per chunk DecodingResult(ids, sum_logprob, avg_logprob, temperature,
         no_speech_prob, compression_ratio, is_silence, attempts): the chosen attempt, the
@@ -1514,6 +1709,9 @@ class WhisperDecoder:
         if no_speech_token is not None and not 0 <= int(no_speech_token) < self.V:
             raise ValueError(f"WhisperDecoder.decode_with_fallback: no_speech_token {no_speech_token} is outside the "
                              f"vocabulary of {self.V}")
+        penalty = (repetition_penalty, no_repeat_ngram_size, history_from)
+        on = self._penalty("decode_with_fallback", [int(t) for t in prompt], max_length, *penalty) is not None
+        extra = {"penalty": penalty} if on else {}  # (at the defaults the passes are called as they always were)
         x = encoder_states
         if not torch.is_tensor(x) or x.dim() != 3:
             raise ValueError("WhisperDecoder.decode_with_fallback: encoder_states must be a [B, P, D] tensor")
@@ -1527,10 +1725,12 @@ class WhisperDecoder:
             probe = (int(sot_index), int(no_speech_token)) if i == 0 and no_speech_token is not None else None
             if T == 0 and int(beam_size) != 1:
                 hyps, ns, prob = self._beam_search(sub, prompt, eot, beam_size, patience, length_penalty, max_length,
-                                                   suppress_tokens, suppress_at_start, kernels, prefill, graph, probe)
+                                                   suppress_tokens, suppress_at_start, kernels, prefill, graph, probe,
+                                                   **extra)
             else:
                 hyps, ns, prob = self._sample(sub, prompt, eot, T, 1 if T == 0 else best_of, int(seed) + i, max_length,
-                                              suppress_tokens, suppress_at_start, kernels, prefill, graph, sync_every, probe)
+                                              suppress_tokens, suppress_at_start, kernels, prefill, graph, sync_every, probe,
+                                              **extra)
             if prob is not None:
                 for b, p in zip(pending, prob.cpu().tolist()):
                     silence_prob[b] = p
