@@ -282,8 +282,11 @@ int wx_conv0_channel_norm_h16(const float* x, int64_t S, int32_t K, int32_t stri
  * o[b, t, h, :] = softmax(scale * q[b, h, t, :] . k[b, h, :, :]^T) v[b, h, :, :], fp32, no mask,
  * head dim D = 64 only.  q/k/v are [B, H, T, 64] with element strides {batch, head, time}
  * (*_strides[0..2]; the head dim is contiguous; rows 16-byte aligned) — transformers' views
- * of the q/k/v projections need no copy; o is [B, T, H, 64] contiguous.  f32 MFMA, not
- * bit-identical to torch's attention (different summation order). */
+ * of the q/k/v projections need no copy; o is [B, T, H, 64] contiguous.  Every stride is a
+ * multiple of 4 floats, and the time strides of k and v lie in [0, 2^23] (a key tile is addressed
+ * by 32-bit byte offsets): anything else is WX_E_INVALID.  f32 MFMA, not bit-identical to torch's
+ * attention (different summation order); bit-identical to wx_prefill_attention_f32 without a mask
+ * on the same views (Tq = Tk = T). */
 int wx_attention_f32(const float* q, const float* k, const float* v, float* o, int32_t B, int32_t H, int32_t T,
                      int32_t D, const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
                      float scale, void* stream);
@@ -313,8 +316,10 @@ int wx_attention_h16(const void* q, const void* k, const void* v, void* o, int32
  * attending only to itself — the reference's one-unpadded-forward-per-segment semantics,
  * alignment.py:217-233).  seg_rows (device, nseg + 1): segment s owns rows [seg_rows[s],
  * seg_rows[s + 1]); seg_units (device, nseg + 1): prefix of H * ceil(T_s / 32), n_units its
- * last entry.  q/k/v element strides {head, row} (*_strides[0..1]); o [rows, H, 64] contiguous.
- * split: waves per 32-query tile (1, 2 or 4; 0 = chosen from n_units). */
+ * last entry.  q/k/v element strides {head, row} (*_strides[0..1]; multiples of 4 floats, the row
+ * strides of k and v in [0, 2^23], as wx_attention_f32's time strides); o [rows, H, 64] contiguous.
+ * split: waves per 32-query tile (1, 2 or 4; 0 = chosen from n_units).  With split 4 a segment's
+ * rows are bit for bit what wx_attention_f32 returns for that segment alone. */
 int wx_attention_f32_packed(const float* q, const float* k, const float* v, float* o, int32_t nseg,
                             const int32_t* seg_rows, const int32_t* seg_units, int32_t n_units, int32_t H, int32_t D,
                             const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, float scale,

@@ -5,8 +5,8 @@
 // packed back to back (the half route of the wav2vec2 emission forward, alignment.py:217-233: one
 // unpadded forward per segment), each segment bit for bit as if launched alone.
 //
-// The structure is attn_f32_kernel's (wx_emission.hip): one workgroup per (batch, head, query tile),
-// whose kSplit waves each take every kSplit-th 32-key tile and merge their (max, sum, O) states
+// The structure is attn_mfma32_unit's (wx_attention_unit.h): one workgroup per (batch, head, query
+// tile), whose kSplit waves each take every kSplit-th 32-key tile and merge their (max, sum, O) states
 // through LDS; the 1-D grid is handed to the XCDs in contiguous runs.  A query tile is kNQ = 2
 // MFMA tiles of 32 queries: every wave holds both, so a K / V tile fetched from L2 serves two S
 // chains and two P V products.  Per wave, key tile and 32 queries:
@@ -37,15 +37,12 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "wx_half.h"
-#include "wx_host.h"  // (and through it include/wx_align.h)
-#include "wx_wave.h"
+#include "wx_attention_unit.h"  // (and through it wx_half.h, wx_host.h, wx_wave.h)
 
 namespace wxh {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using wx::f32x16, wx::s16x4;
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
@@ -56,14 +53,6 @@ constexpr int kQueries = 32 * kNQ;
 constexpr int kRedFloats = kNQ * 34 * 64;    // a wave's state in the merge: per query tile m, sum, 2 x 16 accumulator registers
 constexpr int kLdsBytes = (kSplit - 1) * kRedFloats * 4 > kSplit * kTileBytes ? (kSplit - 1) * kRedFloats * 4
                                                                               : kSplit * kTileBytes;
-
-struct AttnH16Args {
-    const short *q, *k, *v;
-    short* o;  // [B, T, H, 64]
-    int H, T;
-    int64_t sqb, sqh, sqt, skb, skh, skt, svb, svh, svt;  // element strides (head dim: 1)
-    float scale_log2;                                      // softmax scale * log2(e)
-};
 
 // BF: bf16 (else fp16).  Bit patterns travel as shorts (wx_half.h).
 template <bool BF>
@@ -290,53 +279,24 @@ __device__ __forceinline__ void attn_h16_unit(const short* Q, const short* K, co
 // compares: the kernel was bound by the K / V traffic from L2 (8 KB per wave and key tile for 4 + 4
 // MFMAs), which the second query tile halves (B 16, T 1500, fp16: H 8 0.198 -> 0.173 ms, H 20
 // 0.440 -> 0.380 ms).
-template <bool BF>
-__global__ __launch_bounds__(64 * kSplit) __attribute__((amdgpu_waves_per_eu(2))) void attn_h16_kernel(AttnH16Args a) {
+// PACKED (wx_attention_h16_packed): one launch over many segments of their own lengths, 64-query units
+template <bool BF, bool PACKED>
+__global__ __launch_bounds__(64 * kSplit) __attribute__((amdgpu_waves_per_eu(2))) void attn_h16_kernel(wx::AttnArgs a) {
     __shared__ __attribute__((aligned(16))) char lds[kLdsBytes];
-    const int T = a.T;
-    const unsigned w = wx::xcd_unit();  // (head, query tile) units
-    const int nq = (T + kQueries - 1) / kQueries;
-    const int tile = (int)(w % (unsigned)nq);
-    const int bh = (int)(w / (unsigned)nq);
-    const int b = bh / a.H, h = bh % a.H;
-    attn_h16_unit<BF>(a.q + b * a.sqb + h * a.sqh, a.k + b * a.skb + h * a.skh, a.v + b * a.svb + h * a.svh,
-                      a.o + ((int64_t)b * T * a.H + h) * 64, T, tile, a.sqt, a.skt, a.svt, (int64_t)a.H * 64,
-                      a.scale_log2, lds);
-}
-
-// wx_attention_h16_packed: segment s owns rows [seg_rows[s], seg_rows[s + 1]) of q / k / v / o and
-// units [seg_units[s], seg_units[s + 1]) of the grid (H x its 64-query tiles, head-major, so that
-// one (segment, head)'s units are a contiguous run of one XCD)
-struct AttnH16PackedArgs {
-    const short *q, *k, *v;
-    short* o;  // [rows, H, 64]
-    int H, nseg;
-    int64_t sqh, sqt, skh, skt, svh, svt;  // element strides (head dim: 1)
-    float scale_log2;
-    const int32_t* seg_rows;
-    const int32_t* seg_units;
-};
-
-template <bool BF>
-__global__ __launch_bounds__(64 * kSplit) __attribute__((amdgpu_waves_per_eu(2))) void attn_h16_packed_kernel(
-    AttnH16PackedArgs a) {
-    __shared__ __attribute__((aligned(16))) char lds[kLdsBytes];
-    const unsigned w = wx::xcd_unit();  // (head, query tile) units
-    // the segment owning unit w: the last s with seg_units[s] <= w (an empty segment owns no unit,
-    // so the last such s is never one of them: T >= 1 below)
-    int lo = 0, hi = a.nseg - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((unsigned)a.seg_units[mid] <= w) lo = mid;
-        else hi = mid - 1;
+    const short *q = static_cast<const short*>(a.q), *k = static_cast<const short*>(a.k), *v = static_cast<const short*>(a.v);
+    int T, b = 0, h, tile;
+    int64_t row0 = 0;  // first row of this packed segment
+    const unsigned w = wx::xcd_unit();
+    if constexpr (PACKED) {
+        wx::packed_unit(w, a.seg_rows, a.seg_units, a.nseg, kQueries, row0, T, h, tile);
+    } else {
+        T = a.Tq;
+        wx::dense_unit(w, (T + kQueries - 1) / kQueries, a.H, b, h, tile);
     }
-    const int64_t row0 = a.seg_rows[lo];
-    const int T = a.seg_rows[lo + 1] - (int)row0;
-    const int nq = (T + kQueries - 1) / kQueries;
-    const int u = (int)w - a.seg_units[lo];
-    const int tile = u % nq, h = u / nq;
-    attn_h16_unit<BF>(a.q + row0 * a.sqt + h * a.sqh, a.k + row0 * a.skt + h * a.skh, a.v + row0 * a.svt + h * a.svh,
-                      a.o + (row0 * a.H + h) * 64, T, tile, a.sqt, a.skt, a.svt, (int64_t)a.H * 64, a.scale_log2, lds);
+    attn_h16_unit<BF>(q + b * a.qs[0] + h * a.qs[1] + row0 * a.qs[2], k + b * a.ks[0] + h * a.ks[1] + row0 * a.ks[2],
+                      v + b * a.vs[0] + h * a.vs[1] + row0 * a.vs[2],
+                      static_cast<short*>(a.o) + ((row0 + (int64_t)b * T) * a.H + h) * 64, T, tile, a.qs[2], a.ks[2], a.vs[2],
+                      (int64_t)a.H * 64, a.scale_log2, lds);
 }
 
 }  // namespace wxh
@@ -348,35 +308,15 @@ extern "C" int wx_attention_h16(const void* q, const void* k, const void* v, voi
     if (B < 0 || H < 1 || T < 1 || D != 64 || (dtype != WX_DTYPE_F16 && dtype != WX_DTYPE_BF16)) return WX_E_INVALID;
     if (B == 0) return WX_OK;
     if (!q || !k || !v || !o || !q_strides || !k_strides || !v_strides) return WX_E_INVALID;
-    const int64_t* st[3] = {q_strides, k_strides, v_strides};
-    const void* pt[3] = {q, k, v};
-    for (int i = 0; i < 3; ++i) {  // 16-byte reads of 8 elements
-        if ((reinterpret_cast<uintptr_t>(pt[i]) & 15) || (st[i][0] & 7) || (st[i][1] & 7) || (st[i][2] & 7))
-            return WX_E_INVALID;
-    }
-    if (reinterpret_cast<uintptr_t>(o) & 15) return WX_E_INVALID;
-    if (((int64_t)T + kQueries - 1) / kQueries * B * H > INT32_MAX) return WX_E_INVALID;  // (one grid dimension)
-    AttnH16Args a;
-    a.q = static_cast<const short*>(q);
-    a.k = static_cast<const short*>(k);
-    a.v = static_cast<const short*>(v);
-    a.o = static_cast<short*>(o);
+    const int64_t blocks = ((int64_t)T + kQueries - 1) / kQueries * B * H;
+    wx::AttnArgs a{};
+    if (!wx::attn_args(&a, q, k, v, o, q_strides, k_strides, v_strides, 3, 8, false, blocks, scale)) return WX_E_INVALID;
     a.H = H;
-    a.T = T;
-    a.sqb = q_strides[0];
-    a.sqh = q_strides[1];
-    a.sqt = q_strides[2];
-    a.skb = k_strides[0];
-    a.skh = k_strides[1];
-    a.skt = k_strides[2];
-    a.svb = v_strides[0];
-    a.svh = v_strides[1];
-    a.svt = v_strides[2];
-    a.scale_log2 = scale * 1.4426950408889634f;
-    const dim3 grid((unsigned)(((int64_t)T + kQueries - 1) / kQueries * B * H));
+    a.Tq = a.Tk = T;
+    const dim3 grid((unsigned)blocks);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == WX_DTYPE_BF16) hipLaunchKernelGGL(attn_h16_kernel<true>, grid, dim3(64 * kSplit), 0, s, a);
-    else hipLaunchKernelGGL(attn_h16_kernel<false>, grid, dim3(64 * kSplit), 0, s, a);
+    if (dtype == WX_DTYPE_BF16) hipLaunchKernelGGL((attn_h16_kernel<true, false>), grid, dim3(64 * kSplit), 0, s, a);
+    else hipLaunchKernelGGL((attn_h16_kernel<false, false>), grid, dim3(64 * kSplit), 0, s, a);
     return wx::launch_status();
 }
 
@@ -390,31 +330,15 @@ extern "C" int wx_attention_h16_packed(const void* q, const void* k, const void*
         return WX_E_INVALID;
     if (nseg == 0 || n_units == 0) return WX_OK;
     if (!seg_rows || !seg_units) return WX_E_INVALID;
-    const int64_t* st[3] = {q_strides, k_strides, v_strides};
-    const void* pt[3] = {q, k, v};
-    for (int i = 0; i < 3; ++i) {  // 16-byte reads of 8 elements
-        if ((reinterpret_cast<uintptr_t>(pt[i]) & 15) || (st[i][0] & 7) || (st[i][1] & 7)) return WX_E_INVALID;
-    }
-    if (reinterpret_cast<uintptr_t>(o) & 15) return WX_E_INVALID;
-    AttnH16PackedArgs a;
-    a.q = static_cast<const short*>(q);
-    a.k = static_cast<const short*>(k);
-    a.v = static_cast<const short*>(v);
-    a.o = static_cast<short*>(o);
+    wx::AttnArgs a{};  // (strides {head, row}: batch 0)
+    if (!wx::attn_args(&a, q, k, v, o, q_strides, k_strides, v_strides, 2, 8, false, n_units, scale)) return WX_E_INVALID;
     a.H = H;
     a.nseg = nseg;
-    a.sqh = q_strides[0];
-    a.sqt = q_strides[1];
-    a.skh = k_strides[0];
-    a.skt = k_strides[1];
-    a.svh = v_strides[0];
-    a.svt = v_strides[1];
-    a.scale_log2 = scale * 1.4426950408889634f;
     a.seg_rows = seg_rows;
     a.seg_units = seg_units;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)n_units);
-    if (dtype == WX_DTYPE_BF16) hipLaunchKernelGGL(attn_h16_packed_kernel<true>, grid, dim3(64 * kSplit), 0, s, a);
-    else hipLaunchKernelGGL(attn_h16_packed_kernel<false>, grid, dim3(64 * kSplit), 0, s, a);
+    if (dtype == WX_DTYPE_BF16) hipLaunchKernelGGL((attn_h16_kernel<true, true>), grid, dim3(64 * kSplit), 0, s, a);
+    else hipLaunchKernelGGL((attn_h16_kernel<false, true>), grid, dim3(64 * kSplit), 0, s, a);
     return wx::launch_status();
 }

@@ -18,9 +18,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "wx_half.h"
-#include "wx_host.h"  // (and through it include/wx_align.h)
-#include "wx_wave.h"
+#include "wx_attention_unit.h"  // (and through it wx_half.h, wx_host.h, wx_wave.h)
 
 namespace wxe {
 
@@ -364,241 +362,44 @@ __global__ __launch_bounds__(256) void conv0_apply_rl_kernel(const float* __rest
 // wav2vec2 self-attention, fp32 (alignment.py:226-233: the encoder's 12 / 24 attention layers,
 // one unpadded segment per forward, no mask).  torch's fused attention kernel for fp32
 // (aotriton attn_fwd) took 34% of config 3's GPU time at ~26 TFLOP/s (profiles/
-// r2_config3_kernel_stats.csv: 246 us per layer of a 29 s chunk).  Here: a flash-attention
-// forward on the f32-input MFMA (v_mfma_f32_32x32x2_f32: exact f32 fmaf chains, 64 FLOP per
-// clock per SIMD), one workgroup per (batch, head, 32-query tile) whose kAttnSplit waves take
-// every kAttnSplit-th 32-key tile (a single 30 s segment has only 12 x 47 query tiles) and
-// merge their (max, sum, O) states through LDS at the end; per wave:
-//   * S^T = K Q^T per 32-key tile: lane l holds key row (l & 31) of K and query row (l & 31)
-//     of Q as the A / B operands; the head dimension is split 32 / 32 between the lane halves
-//     (the contraction order is free), so each lane reads contiguous 128-B half rows;
-//   * S^T's accumulator has the query on the lane and 16 keys per lane in registers, so the
-//     online softmax is lane-local plus one exchange with the other lane half, and the same
-//     registers are the B operand (P^T) of O^T += V^T P^T without any lane movement: MFMA j
-//     takes key (j & 3) + 8 (j >> 2) + 4 (l >> 5) from each half, and V is read at those rows;
-//   * O^T lives in two 32x32 accumulators (head dims 0-31, 32-63), rescaled lane-locally.
+// r2_config3_kernel_stats.csv: 246 us per layer of a 29 s chunk).  Here: attn_mfma32_unit
+// (wx_attention_unit.h: the flash-attention forward on the f32-input MFMA, square and unmasked),
+// one workgroup per (batch, head, 32-query tile) whose SPLIT waves take every SPLIT-th 32-key tile
+// (a single 30 s segment has only 12 x 47 query tiles).
 // Not bit-identical to torch's kernel (different summation order); tests compare it with
 // torch's attention at fp32 tolerance and the whole prepared forward with the stock one.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct AttnArgs {
-    const float* q;
-    const float* k;
-    const float* v;
-    float* o;  // [B, T, H, 64] (packed: [rows, H, 64])
-    int B, H, T;
-    int64_t sqb, sqh, sqt, skb, skh, skt, svb, svh, svt;  // element strides (head dim: 1)
-    float scale_log2;                                      // softmax scale * log2(e)
-    // packed segments (wx_attention_f32_packed): segment s owns rows [seg_rows[s], seg_rows[s+1])
-    // and work units [seg_units[s], seg_units[s+1]) (H x its 32-query tiles, head-major)
-    const int32_t* seg_rows;
-    const int32_t* seg_units;
-    int nseg;
-};
-
 constexpr int kAttnSplit = 4;  // waves per 32-query tile, each over every kAttnSplit-th 32-key tile
 
 // amdgpu_waves_per_eu(2): two waves per SIMD, stated so the allocator keeps everything in VGPRs
-// (~230 with the buffer-descriptor loads) instead of splitting them with AGPR copies (A/B: 1-2%
-// faster).  A third wave per SIMD (168 registers: V loaded behind the S chain instead of a tile
-// ahead, 2 spills) was 10-15% slower.  Round 6: the K / V loads through per-tile buffer
-// descriptors (no per-lane address arithmetic) and no key compare on whole tiles took 12 packed
-// 30 s segments (H = 12) from 818 to 727 us per call; PMC before the change: 327 VALU
-// instructions per (wave, key tile) beside 64 MFMAs, ~150 of them address arithmetic (32-bit
-// multiplies and 64-bit adds), MFMA busy 65% of the cycles.  With it the software-pipelined
-// one-wave form of the same kernel (tile k + 1's S chain beside tile k's softmax, +2% before)
-// measured equal (729 us) and was removed.
-// SPLIT waves per 32-query tile (each over every SPLIT-th 32-key tile; SPLIT = 1: one wave, no
-// merge); PACKED: one launch over many segments of their own lengths (rows packed back to back)
+// instead of splitting them with AGPR copies (A/B: 1-2% faster).  A third wave per SIMD (168
+// registers: V loaded behind the S chain instead of a tile ahead, 2 spills) was 10-15% slower.
+// Round 6: the K / V loads through per-tile buffer descriptors (no per-lane address arithmetic) and
+// no key compare on whole tiles took 12 packed 30 s segments (H = 12) from 818 to 727 us per call;
+// PMC before the change: 327 VALU instructions per (wave, key tile) beside 64 MFMAs, ~150 of them
+// address arithmetic (32-bit multiplies and 64-bit adds), MFMA busy 65% of the cycles.  With it the
+// software-pipelined one-wave form of the same kernel (tile k + 1's S chain beside tile k's softmax,
+// +2% before) measured equal (729 us) and was removed.  On the shared body (213-215 VGPRs) the same
+// call measured 717 / 730 / 719 us at SPLIT 1 / 2 / 4 beside 722 / 734 / 725 us for the kernel it
+// replaced, in one session.
+// SPLIT waves per 32-query tile (SPLIT = 1: one wave, no merge); PACKED: one launch over many
+// segments of their own lengths (rows packed back to back: wx_attention_f32_packed)
 template <int SPLIT, bool PACKED>
-__global__ __launch_bounds__(64 * SPLIT) __attribute__((amdgpu_waves_per_eu(2))) void attn_f32_kernel(AttnArgs a) {
-    int T, tile, h;
-    int64_t row0;  // o row of query 0 of this batch entry / segment
-    const float *Q, *K, *V;
-    const unsigned w = wx::xcd_unit();  // (head, query tile) units
-    if (PACKED) {
-        // the segment owning unit w: the last s with seg_units[s] <= w (empty segments own no
-        // units, so the last such s is never one of them)
-        int lo = 0, hi = a.nseg - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if ((unsigned)a.seg_units[mid] <= w) lo = mid;
-            else hi = mid - 1;
-        }
-        row0 = a.seg_rows[lo];
-        T = a.seg_rows[lo + 1] - (int)row0;
-        const int nq = (T + 31) / 32;
-        const int u = (int)w - a.seg_units[lo];
-        tile = u % nq;
-        h = u / nq;
-        Q = a.q + row0 * a.sqt + h * a.sqh;
-        K = a.k + row0 * a.skt + h * a.skh;
-        V = a.v + row0 * a.svt + h * a.svh;
+__global__ __launch_bounds__(64 * SPLIT) __attribute__((amdgpu_waves_per_eu(2))) void attn_f32_kernel(wx::AttnArgs a) {
+    const float *q = static_cast<const float*>(a.q), *k = static_cast<const float*>(a.k), *v = static_cast<const float*>(a.v);
+    int T, b = 0, h, tile;
+    int64_t row0 = 0;  // first row of this packed segment
+    const unsigned w = wx::xcd_unit();
+    if constexpr (PACKED) {
+        wx::packed_unit(w, a.seg_rows, a.seg_units, a.nseg, 32, row0, T, h, tile);
     } else {
-        T = a.T;
-        const int nq = (T + 31) / 32;
-        tile = (int)(w % (unsigned)nq);
-        const int bh = (int)(w / (unsigned)nq);
-        const int b = bh / a.H;
-        h = bh % a.H;
-        row0 = (int64_t)b * T;
-        Q = a.q + b * a.sqb + h * a.sqh;
-        K = a.k + b * a.skb + h * a.skh;
-        V = a.v + b * a.svb + h * a.svh;
+        T = a.Tq;
+        wx::dense_unit(w, (T + 31) / 32, a.H, b, h, tile);
     }
-    const int q0 = tile * 32;
-    const int l = threadIdx.x & 63, r = l & 31, hf = l >> 5, wv = threadIdx.x >> 6;
-    float qv[32];
-    {
-        const float4* qp = reinterpret_cast<const float4*>(Q + (int64_t)min(q0 + r, T - 1) * a.sqt + 32 * hf);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const float4 x = qp[i];
-            qv[4 * i] = x.x;
-            qv[4 * i + 1] = x.y;
-            qv[4 * i + 2] = x.z;
-            qv[4 * i + 3] = x.w;
-        }
-    }
-    f32x16 o0, o1;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) o0[i] = o1[i] = 0.f;
-    float m = -INFINITY, lsum = 0.f;
-    // K / V of the wave's next key tile are loaded while the current one computes, through
-    // buffer descriptors rebased per key tile (as attn_f32_pipe_kernel: no per-lane address
-    // arithmetic; keys past the end read zeros, masked like the clamped re-reads they replace)
-    float kv[32], va[16], vb[16];  // K[key r][32 hf + j]; V[key(j)][r], V[key(j)][32 + r]
-    const int64_t skt = a.skt, svt = a.svt;
-    const int vk = (int)((r * skt + 32 * hf) * 4), vv = (int)((4 * hf * svt + r) * 4);
-    auto tile_rsrc = [&](const float* base, int64_t stride, int k0) {
-        k0 = __builtin_amdgcn_readfirstlane(k0);  // (32 wv + ...: uniform, which hipcc cannot prove)
-        const int64_t rem = (int64_t)(T - 1 - k0) * stride + 64;
-        const int n = rem <= 0 ? 0 : (int)min(rem * 4, (int64_t)0x7fffffff);
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base + (int64_t)k0 * stride), 0, n, 0x00020000);
-    };
-    auto load_kv = [&](int k0, float(&kk)[32], float(&a0)[16], float(&a1)[16]) {
-        typedef unsigned u4 __attribute__((ext_vector_type(4)));
-        const __amdgpu_buffer_rsrc_t rk = tile_rsrc(K, skt, k0), rv = tile_rsrc(V, svt, k0);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const u4 x = __builtin_bit_cast(u4, __builtin_amdgcn_raw_buffer_load_b128(rk, vk + 16 * i, 0, 0));
-            kk[4 * i] = __uint_as_float(x.x);
-            kk[4 * i + 1] = __uint_as_float(x.y);
-            kk[4 * i + 2] = __uint_as_float(x.z);
-            kk[4 * i + 3] = __uint_as_float(x.w);
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int so = (int)(((j & 3) + 8 * (j >> 2)) * svt * 4);
-            a0[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rv, vv, so, 0));
-            a1[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rv, vv + 128, so, 0));
-        }
-    };
-    if (32 * wv < T) load_kv(32 * wv, kv, va, vb);
-    for (int k0 = 32 * wv; k0 < T; k0 += 32 * SPLIT) {
-        f32x16 s;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) s[i] = 0.f;
-#pragma unroll
-        for (int j = 0; j < 32; ++j) s = __builtin_amdgcn_mfma_f32_32x32x2f32(kv[j], qv[j], s, 0, 0, 0);
-        float van[16], vbn[16];
-        load_kv(k0 + 32 * SPLIT, kv, van, vbn);  // (past the end: zeros, unused); kv is dead once the S chain has been issued
-        float mx = -INFINITY;
-        if (k0 + 32 <= T) {  // a whole key tile: no key compare (uniform branch)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                s[i] = s[i] * a.scale_log2;
-                mx = fmaxf(mx, s[i]);
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int key = k0 + (i & 3) + 8 * (i >> 2) + 4 * hf;
-                const float x = key < T ? s[i] * a.scale_log2 : -INFINITY;
-                s[i] = x;
-                mx = fmaxf(mx, x);
-            }
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float mn = fmaxf(m, mx);
-        const float alpha = __builtin_amdgcn_exp2f(m - mn);
-        float ps = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const float p = __builtin_amdgcn_exp2f(s[i] - mn);
-            s[i] = p;
-            ps += p;
-        }
-        ps += __shfl_xor(ps, 32);
-        lsum = lsum * alpha + ps;
-        m = mn;
-        if (__any(alpha != 1.0f)) {  // (the running maximum settles after a few tiles)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                o0[i] *= alpha;
-                o1[i] *= alpha;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(va[j], s[j], o0, 0, 0, 0);
-            o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(vb[j], s[j], o1, 0, 0, 0);
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            va[j] = van[j];
-            vb[j] = vbn[j];
-        }
-    }
-    // merge the waves' partial softmax states (m, lsum, O^T) in wave 0
-    if constexpr (SPLIT > 1) {
-    __shared__ float red[SPLIT - 1][34][64];
-    if (wv > 0) {
-        float* o = &red[wv - 1][0][l];
-        o[0] = m;
-        o[64] = lsum;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            o[64 * (2 + i)] = o0[i];
-            o[64 * (18 + i)] = o1[i];
-        }
-    }
-    __syncthreads();
-    if (wv > 0) return;
-    float mt = m;
-#pragma unroll
-    for (int w = 0; w < SPLIT - 1; ++w) mt = fmaxf(mt, red[w][0][l]);
-    {
-        const float c = __builtin_amdgcn_exp2f(m - mt);
-        lsum *= c;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            o0[i] *= c;
-            o1[i] *= c;
-        }
-    }
-#pragma unroll
-    for (int w = 0; w < SPLIT - 1; ++w) {
-        const float c = __builtin_amdgcn_exp2f(red[w][0][l] - mt);  // a wave without keys: 0
-        lsum += red[w][1][l] * c;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            o0[i] += red[w][2 + i][l] * c;
-            o1[i] += red[w][18 + i][l] * c;
-        }
-    }
-    }
-    if (q0 + r >= T) return;
-    const float inv = 1.0f / lsum;
-    float* orow = a.o + ((row0 + q0 + r) * a.H + h) * 64;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {  // registers 4g..4g+3: head dims 8g + 4hf + 0..3
-        const int d = 8 * g + 4 * hf;
-        *reinterpret_cast<float4*>(orow + d) =
-            make_float4(o0[4 * g] * inv, o0[4 * g + 1] * inv, o0[4 * g + 2] * inv, o0[4 * g + 3] * inv);
-        *reinterpret_cast<float4*>(orow + 32 + d) =
-            make_float4(o1[4 * g] * inv, o1[4 * g + 1] * inv, o1[4 * g + 2] * inv, o1[4 * g + 3] * inv);
-    }
+    wx::attn_mfma32_unit<wx::kF32, SPLIT>(q + b * a.qs[0] + h * a.qs[1] + row0 * a.qs[2],
+                                          k + b * a.ks[0] + h * a.ks[1] + row0 * a.ks[2],
+                                          v + b * a.vs[0] + h * a.vs[1] + row0 * a.vs[2],
+                                          static_cast<float*>(a.o) + ((row0 + (int64_t)b * T) * a.H + h) * 64, T, T, -1, tile,
+                                          a.qs[2], a.ks[2], a.vs[2], (int64_t)a.H * 64, a.scale_log2);
 }
 
 // ------------------------------------------------------------------------------------
@@ -860,40 +661,16 @@ extern "C" int wx_attention_f32(const float* q, const float* k, const float* v, 
     if (B < 0 || H <= 0 || T < 0 || D != 64 || !q || !k || !v || !o || !q_strides || !k_strides || !v_strides)
         return WX_E_INVALID;
     if (B == 0 || T == 0) return WX_OK;
-    if ((int64_t)(T + 31) / 32 * B * H > INT32_MAX) return WX_E_INVALID;  // (one grid dimension)
-    const int64_t* st[3] = {q_strides, k_strides, v_strides};
-    const float* pt[3] = {q, k, v};
-    for (int i = 0; i < 3; ++i) {  // 16-byte rows (float4 reads of Q / K)
-        if ((reinterpret_cast<uintptr_t>(pt[i]) & 15) || (st[i][0] & 3) || (st[i][1] & 3) || (st[i][2] & 3))
-            return WX_E_INVALID;
-    }
-    if (reinterpret_cast<uintptr_t>(o) & 15) return WX_E_INVALID;
-    AttnArgs a;
-    a.q = q;
-    a.k = k;
-    a.v = v;
-    a.o = o;
-    a.B = B;
+    const int64_t blocks = ((int64_t)T + 31) / 32 * B * H;
+    wx::AttnArgs a{};
+    if (!wx::attn_args(&a, q, k, v, o, q_strides, k_strides, v_strides, 3, 4, true, blocks, scale)) return WX_E_INVALID;
     a.H = H;
-    a.T = T;
-    a.sqb = q_strides[0];
-    a.sqh = q_strides[1];
-    a.sqt = q_strides[2];
-    a.skb = k_strides[0];
-    a.skh = k_strides[1];
-    a.skt = k_strides[2];
-    a.svb = v_strides[0];
-    a.svh = v_strides[1];
-    a.svt = v_strides[2];
-    a.scale_log2 = scale * 1.4426950408889634f;
-    a.seg_rows = a.seg_units = nullptr;
-    a.nseg = 0;
-    const dim3 grid((unsigned)((int64_t)(T + 31) / 32 * B * H));
+    a.Tq = a.Tk = T;
+    const dim3 grid((unsigned)blocks);
     hipLaunchKernelGGL((attn_f32_kernel<kAttnSplit, false>), grid, dim3(64 * kAttnSplit), 0,
                        reinterpret_cast<hipStream_t>(stream), a);
     return wx::launch_status();
 }
-
 
 extern "C" int wx_attention_f32_packed(const float* q, const float* k, const float* v, float* o, int32_t nseg,
                                        const int32_t* seg_rows, const int32_t* seg_units, int32_t n_units,
@@ -905,28 +682,9 @@ extern "C" int wx_attention_f32_packed(const float* q, const float* k, const flo
         return WX_E_INVALID;
     if (nseg == 0 || n_units == 0) return WX_OK;
     if (!seg_rows || !seg_units) return WX_E_INVALID;
-    const int64_t* st[3] = {q_strides, k_strides, v_strides};
-    const float* pt[3] = {q, k, v};
-    for (int i = 0; i < 3; ++i) {  // 16-byte rows (float4 reads of Q / K)
-        if ((reinterpret_cast<uintptr_t>(pt[i]) & 15) || (st[i][0] & 3) || (st[i][1] & 3)) return WX_E_INVALID;
-    }
-    if (reinterpret_cast<uintptr_t>(o) & 15) return WX_E_INVALID;
-    AttnArgs a;
-    a.q = q;
-    a.k = k;
-    a.v = v;
-    a.o = o;
-    a.B = 1;
+    wx::AttnArgs a{};  // (strides {head, row}: batch 0)
+    if (!wx::attn_args(&a, q, k, v, o, q_strides, k_strides, v_strides, 2, 4, true, n_units, scale)) return WX_E_INVALID;
     a.H = H;
-    a.T = 0;
-    a.sqb = a.skb = a.svb = 0;
-    a.sqh = q_strides[0];
-    a.sqt = q_strides[1];
-    a.skh = k_strides[0];
-    a.skt = k_strides[1];
-    a.svh = v_strides[0];
-    a.svt = v_strides[1];
-    a.scale_log2 = scale * 1.4426950408889634f;
     a.seg_rows = seg_rows;
     a.seg_units = seg_units;
     a.nseg = nseg;
